@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: frames/sec through the PlaneRCNN detector at 480x640 on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 and no torchrun environment: this process spawns the N ranks itself (python -m torch.distributed.run,
 one rank per GPU, RCCL) BEFORE it touches the GPU and relays rank 0's JSON line; under the driver's own
@@ -12,7 +12,10 @@ detector: normalise -> ResNet50-FPN -> RPN (top-k, NMS) -> ROIAlign -> box head 
 plane / axis heads -> depth head -> fused post-process + mask paste + plane-offset LSQ -> packed detection
 records (+ an RCCL all-gather of the records when N > 1: frames are sharded across ranks, weak scaling).
 Weights: random init of the reference architecture with calibrated batch-norm statistics (no checkpoint is
-available offline); fp32 end to end.  Prints ONE JSON line on rank 0; besides the contract fields it carries
+available offline); fp32 end to end.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if `--dump-outputs DIR` is given (dump_outputs)
+and prints the contract fields and `config`.  With `--full` the line carries, besides them (each `--no-...` flag drops its leg)
   roofline            dominant kernel: EXECUTED matrix FLOPs / fp32-MFMA peak (frac), algorithmic_speedup separately
   operating_points    SURVEY 8d: A (thresh 0.7, D=0), B (0.0, D=100), C (4 injected boxes per frame through given_boxes)
   value_with_transfers the same step with the uint8 clip copied H2D and the packed records D2H inside the timed region
@@ -115,6 +118,12 @@ def parse_args():
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL over xGMI; the default) or gloo (test rigs with fewer GPUs than ranks)")
     ap.add_argument("--cpu-frames", type=int, default=12, help="timed frames of the bounded CPU-baseline sample (~10-20 s of host work)")
     ap.add_argument("--no-train-leg", action="store_true", help="skip the short training-step leg (BASELINE configs[4]: `train_step` in the line)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: roofline (an instrumented step and HIP events around the "
+                         "dominant kernel's timed launches), operating points, transfer-inclusive loop, other arithmetics, CPU baseline and "
+                         "matched detections, per-frame loop, training legs, collective record.  Off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64; see dump_outputs)")
     return ap.parse_args()
 
 
@@ -239,6 +248,53 @@ def dominant_roofline(per, step_sec=None):
     return r
 
 
+DEPTH_SAMPLE = 1 << 20  # depth pixels kept by dump_outputs (the whole map is 79 MB at 64 frames)
+
+
+def dump_outputs(out, path: str) -> dict:
+    """`--dump-outputs DIR`: the BatchedOutput of the last timed step (what `model.inference_batched` hands its caller) as
+    DIR/<name>.npy.  Real values as float32, counts, classes and flags as float64 (exact).  Detection slots past a frame's live
+    count hold no result and are written as zeros, so that two builds compare slot for slot; the depth maps as the same seeded
+    sample of DEPTH_SAMPLE pixels every run (`depth_sample_index` holds the flat indices).  ~33 MB at 64 frames.
+    Returns {name: shape}."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    det = out.det
+
+    def live(count, n):  # [B, n] bool: slot r of frame b holds a result
+        return torch.arange(n, device=count.device)[None, :] < count.long()[:, None]
+
+    def masked(t, keep):
+        return torch.where(keep.view(*keep.shape, *([1] * (t.dim() - 2))), t, torch.zeros((), dtype=t.dtype, device=t.device))
+
+    R = det.boxes.shape[1]
+    dl = live(det.count, R)
+    arrays = {
+        "det_count": det.count, "det_boxes": masked(det.boxes, dl), "det_scores": masked(det.scores, dl),
+        "det_classes": masked(det.classes, dl),
+        "keep": masked(out.keep, dl), "boxes": masked(out.boxes, dl), "planes": masked(out.planes, dl), "area": masked(out.area, dl),
+        "rec_count": out.rec_count, "records": masked(out.records, live(out.rec_count, out.records.shape[1])),
+    }
+    if out.proposals is not None:
+        pb, pl, _level, _pos, pc = out.proposals
+        pv = live(pc, pb.shape[1])
+        arrays.update(proposal_count=pc, proposal_boxes=masked(pb, pv), proposal_logits=masked(pl, pv))
+    if out.depth is not None:
+        n = out.depth.numel()
+        idx = np.sort(np.random.default_rng(2020).choice(n, min(n, DEPTH_SAMPLE), replace=False))
+        arrays["depth_sample"] = out.depth.reshape(-1)[torch.from_numpy(idx).to(out.depth.device)]
+        arrays["depth_sample_index"] = torch.from_numpy(idx)
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def main():
     args = parse_args()
     env_world = os.environ.get("WORLD_SIZE")
@@ -351,21 +407,22 @@ def main():
         step()
     drain()
     barrier()
-    # One fully instrumented step OUTSIDE the timed region (HIP events around every conv-GEMM launch, on the launch stream): the
-    # per-kernel table (`all_conv_kernels`) and the ranking that names the dominant kernel.  Inside the timed region only the
-    # dominant kernel's launches carry events -- ~700 event pairs per step cost 0.8 ms of its 44, and the headline does not pay
-    # for the table.
-    ops.CONV_TIMING = []
-    step()
-    drain()
-    barrier()
-    survey, ops.CONV_TIMING = ops.CONV_TIMING, None
-    tot = {}
-    for t in survey:
-        tot[t[0]] = tot.get(t[0], 0.0) + t[2].elapsed_time(t[3])
-    dominant = max(tot.items(), key=lambda kv: kv[1])[0]
-    ops.CONV_TIMING_ONLY = frozenset({dominant})
-    ops.CONV_TIMING = []
+    if args.full:
+        # One fully instrumented step OUTSIDE the timed region (HIP events around every conv-GEMM launch, on the launch stream): the
+        # per-kernel table (`all_conv_kernels`) and the ranking that names the dominant kernel.  Inside the timed region only the
+        # dominant kernel's launches carry events -- ~700 event pairs per step cost 0.8 ms of its 44, and the headline does not pay
+        # for the table.
+        ops.CONV_TIMING = []
+        step()
+        drain()
+        barrier()
+        survey, ops.CONV_TIMING = ops.CONV_TIMING, None
+        tot = {}
+        for t in survey:
+            tot[t[0]] = tot.get(t[0], 0.0) + t[2].elapsed_time(t[3])
+        dominant = max(tot.items(), key=lambda kv: kv[1])[0]
+        ops.CONV_TIMING_ONLY = frozenset({dominant})
+        ops.CONV_TIMING = []
     from articulation3d_amd import parallel as _par
 
     _par.STATS.update(calls=0, bytes=0, host_s=0.0)
@@ -376,11 +433,36 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     parallel_stats = dict(_par.STATS)
-    timing, ops.CONV_TIMING, ops.CONV_TIMING_ONLY = ops.CONV_TIMING, None, None
-    timing = [t for t in timing if t[0] == dominant]  # (a launch seen for the first time is instrumented whatever its label)
+    if args.full:
+        timing, ops.CONV_TIMING, ops.CONV_TIMING_ONLY = ops.CONV_TIMING, None, None
+        timing = [t for t in timing if t[0] == dominant]  # (a launch seen for the first time is instrumented whatever its label)
     elapsed = max_over_ranks(elapsed)
     total_frames = B * world * args.steps
     fps = total_frames / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+
+    dets = out.rec_count.float().mean().item()
+    raw = out.det.count.float().mean().item()
+    result = {
+        "metric": "frames/sec through PlaneRCNN detector at 480x640",
+        "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": DTYPES[args.precision], "data": "synthetic",
+        "config": {"workload": "BASELINE configs[2]: full PlaneRCNN detector (ResNet50-FPN + RPN + ROIAlign + box/mask/plane/axis heads "
+                               "+ depth head + NMS + mask paste + plane-offset LSQ + record pack), random-init weights with "
+                               "calibrated BN, synthetic 480x640 uint8 frames resident in HBM (arithmetic: see `dtype`)",
+                   "frames_per_step_per_gpu": B, "global_frames_per_step": B * world, "score_thresh_test": args.score_thresh,
+                   "raw_detections_per_frame": round(raw, 2), "kept_detections_per_frame": round(dets, 2),
+                   "proposals_per_frame": round(out.proposals[4].float().mean().item(), 1),
+                   "sharding": "contiguous frame blocks per rank" + (", RCCL all-gather of detection records per step" if world > 1 else "")},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+        return
 
     # ---- the same step with the transfers SURVEY 8d puts in the region: uint8 clip H2D (pinned) and packed records D2H
     extra = {}
@@ -502,9 +584,6 @@ def main():
             alt[other] = {"value": round(B * world * n_alt / el, 2), "unit": "frames/s", "ms_per_step": round(1e3 * el / n_alt, 3), "steps": n_alt,
                           "dtype": DTYPES[other], "roofline": alt_roof, "note": "python bench.py --precision " + other}
 
-    dets = out.rec_count.float().mean().item()
-    raw = out.det.count.float().mean().item()
-
     # roofline of the dominant kernel: per kernel sums of FLOPs and HIP-event durations over the timed steps.  Names are the
     # dispatcher's own record of what it launched (a3d_last_conv_variant), not a host-side mirror of its rules.
     per, per_main, stream_sec = {}, {}, {}
@@ -596,18 +675,7 @@ def main():
     roofline["conv_kernels_share_of_step_time"] = round(conv_sec / step_sec, 3)
     roofline["whole_step_fp32_equivalent_tflops"] = round(sum(v[3] for v in per_all.values()) / step_sec / 1e12, 2)
 
-    result = {
-        "metric": "frames/sec through PlaneRCNN detector at 480x640",
-        "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": DTYPES[args.precision], "data": "synthetic",
-        "config": {"workload": "BASELINE configs[2]: full PlaneRCNN detector (ResNet50-FPN + RPN + ROIAlign + box/mask/plane/axis heads "
-                               "+ depth head + NMS + mask paste + plane-offset LSQ + record pack), random-init weights with "
-                               "calibrated BN, synthetic 480x640 uint8 frames resident in HBM (arithmetic: see `dtype`)",
-                   "frames_per_step_per_gpu": B, "global_frames_per_step": B * world, "score_thresh_test": args.score_thresh,
-                   "raw_detections_per_frame": round(raw, 2), "kept_detections_per_frame": round(dets, 2),
-                   "proposals_per_frame": round(out.proposals[4].float().mean().item(), 1),
-                   "sharding": "contiguous frame blocks per rank" + (", RCCL all-gather of detection records per step" if world > 1 else "")},
+    result.update({
         "roofline": roofline,
         # SURVEY 8d's definition of the metric puts the transfers inside the clock: the same step with the uint8 clip copied H2D and
         # the packed records copied D2H in the timed region (details under `value_with_transfers`); `value` has the clip resident
@@ -615,7 +683,7 @@ def main():
             "ms_per_step_transfer_inclusive": extra["value_with_transfers"]["ms_per_step"]} if "value_with_transfers" in extra else {}),
         **extra,
         **({"alt_modes": alt} if alt else {}),
-    }
+    })
     result["roi_out_of_window"] = ops.roi_window_count(dev) if args.precision == "fp16x2" else None  # (the window monitor: 0 expected)
     # What a SCALE run needs to show that the collective backend saw N distinct GPUs: every rank's device identity, gathered over the group
     # (the reference's analogue: detectron2's launch + comm.gather, tools/train_net.py:110-117, evaluation/arti_evaluation.py:195-199).

@@ -86,7 +86,7 @@ def test_inference_script_sharded_over_two_ranks(tmp_path):
 def test_bench_spawns_its_ranks(tmp_path):
     """`python bench.py --gpus 2` outside torchrun must launch two ranks and report n_gpus = 2 (the flag was dead)."""
     r = _run(["bench.py", "--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--batch", "4",
-              "--cpu-frames", "2", "--no-alt-modes", "--no-operating-points"], timeout=1500)
+              "--cpu-frames", "2", "--no-alt-modes", "--no-operating-points", "--full"], timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 2 and d["config"]["global_frames_per_step"] == 8 and d["scaling"] == "weak" and d["value"] > 0
@@ -110,7 +110,7 @@ def test_bench_with_eight_ranks_reports_eight(tmp_path):
     step's records are all-gathered, rank 0 runs the CPU leg and the matched-detections check while the others wait at the barrier,
     and the line says n_gpus = 8 with whole-job frames per step."""
     r = _run(["bench.py", "--gpus", "8", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--batch", "2",
-              "--cpu-frames", "2", "--no-alt-modes", "--no-operating-points", "--no-train-leg"], timeout=1800)
+              "--cpu-frames", "2", "--no-alt-modes", "--no-operating-points", "--no-train-leg", "--full"], timeout=1800)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 8 and d["config"]["global_frames_per_step"] == 16 and d["scaling"] == "weak" and d["value"] > 0
@@ -133,8 +133,8 @@ def test_two_real_rccl_ranks_bench_and_inference(tmp_path):
     single-process run.  Skips itself on the 1-GPU boxes of the development pool."""
     import socket
 
-    r = _run(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--cpu-frames", "2", "--no-alt-modes", "--no-operating-points"],
-             timeout=1500)
+    r = _run(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--cpu-frames", "2", "--no-alt-modes", "--no-operating-points",
+              "--full"], timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 2 and d["config"]["global_frames_per_step"] == 16 and "cpu_baseline" in d and d["matched_detections"]["matched"] is True
@@ -159,8 +159,8 @@ def test_two_real_rccl_ranks_bench_and_inference(tmp_path):
 
 def test_bench_single_rank_rccl_gather(tmp_path):
     """The nccl (= RCCL) process group and the asynchronous all-gather of the detection records, with one rank on this box."""
-    r = _run(["bench.py", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-alt-modes", "--no-operating-points", "--no-train-leg"],
-             env=dict(ENV, A3D_BENCH_FORCE_DIST="1"))
+    r = _run(["bench.py", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-alt-modes", "--no-operating-points", "--no-train-leg",
+              "--full"], env=dict(ENV, A3D_BENCH_FORCE_DIST="1"))
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
     assert d["collective"]["backend"] == "nccl" and d["collective"]["world"] == 1 and d["collective"]["devices"][0]["pci"]
@@ -169,7 +169,8 @@ def test_bench_single_rank_rccl_gather(tmp_path):
 
 
 def test_bench_default_line_has_the_contract_fields():
-    r = _run(["bench.py", "--steps", "2", "--warmup", "1", "--batch", "16", "--cpu-frames", "2", "--no-alt-modes"], timeout=1500)
+    """The line of `--full` (every leg but the other arithmetics): the contract fields and what the full run adds to them."""
+    r = _run(["bench.py", "--steps", "2", "--warmup", "1", "--batch", "16", "--cpu-frames", "2", "--no-alt-modes", "--full"], timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
@@ -206,6 +207,36 @@ def test_bench_default_line_has_the_contract_fields():
     assert set(rf["operating_points"]) == {"A", "B", "C"} and rf["operating_points"]["B"]["value"] == d["operating_points"]["B_thresh0.0"]["value"]
     assert rf["loop_b1"]["frames"] == 64 and rf["loop_b1"]["frames_per_s"] > 50 and rf["loop_b1"]["detections_per_frame"] > 0
     assert set(rf["train_step"]) == {"images_per_gpu_2", "images_per_gpu_16"} and rf["train_step"]["images_per_gpu_2"]["exposed_exchange_ms"] == c["exposed_ms"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the contract fields and `config` alone; `--dump-outputs DIR` writes
+    what the last timed step returned as float .npy files within 64 MB, and two runs with the same arguments agree on them."""
+    import numpy as np
+
+    lines = []
+    for k in ("a", "b"):
+        r = _run(["bench.py", "--steps", "3", "--warmup", "1", "--batch", "8", "--dump-outputs", str(tmp_path / k)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(_json_line(r.stdout))
+    d = lines[0]
+    assert set(d) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                      "dtype", "data", "config"}, sorted(d)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] - 8e3) < 0.01 * 8e3  # (8 frames per step)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"records.npy", "rec_count.npy", "det_boxes.npy", "det_scores.npy", "planes.npy", "depth_sample.npy"} <= set(names), names
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape, n
+        scale = max(1.0, float(np.abs(a).max()))
+        assert float(np.abs(a - b).max()) <= 1e-4 * scale, n
+        total += a.nbytes
+    assert total <= 64 << 20
+    rc = np.load(tmp_path / "a" / "rec_count.npy")
+    assert rc.shape == (8,) and abs(rc.mean() - d["config"]["kept_detections_per_frame"]) < 0.01
 
 
 def test_first_small_batch_of_a_process_equals_the_steady_state():

@@ -27,26 +27,26 @@ def test_config_defaults_and_reference_yaml():
     c2.defrost()
     c2.MODEL.DEVICE = "cuda"
     assert cfg.MODEL.DEVICE == "cpu"
-    ref = "/root/reference/articulation3d/config/config.yaml"
-    if os.path.exists(ref):  # the reference's own YAML loads verbatim and agrees with ours on every shared key
-        from articulation3d_amd.config import get_cfg, get_planercnn_cfg_defaults
+    # the reference's own YAML (its config/config.yaml, stored verbatim as a fixture) loads and agrees with ours on every shared key
+    ref = os.path.join(ROOT, "tests", "golden", "reference_config.yaml")
+    from articulation3d_amd.config import get_cfg, get_planercnn_cfg_defaults
 
-        r = get_cfg()
-        get_planercnn_cfg_defaults(r)
-        r.merge_from_file(ref)
-        import yaml
+    r = get_cfg()
+    get_planercnn_cfg_defaults(r)
+    r.merge_from_file(ref)
+    import yaml
 
-        ours = yaml.safe_load(open(os.path.join(ROOT, "configs", "planercnn_inference.yaml")))
+    ours = yaml.safe_load(open(os.path.join(ROOT, "configs", "planercnn_inference.yaml")))
 
-        def walk(a, b, path=""):  # every key our inference YAML sets has the reference's value
-            for k, v in a.items():
-                assert k in b, path + k
-                if isinstance(v, dict):
-                    walk(v, b[k], path + k + ".")
-                else:
-                    assert (list(v) == list(b[k])) if isinstance(v, (list, tuple)) else (v == b[k]), path + k
+    def walk(a, b, path=""):  # every key our inference YAML sets has the reference's value
+        for k, v in a.items():
+            assert k in b, path + k
+            if isinstance(v, dict):
+                walk(v, b[k], path + k + ".")
+            else:
+                assert (list(v) == list(b[k])) if isinstance(v, (list, tuple)) else (v == b[k]), path + k
 
-        walk(ours, r)
+    walk(ours, r)
 
 
 def test_registries_resolve_reference_names():

@@ -35,11 +35,20 @@ def test_plane_head_matches_reference(oracle, golden_dir):
 
 
 def test_axis_head_matches_reference(oracle, golden_dir):
+    """In float64 the oracle gives the reference module's float64 outputs (the fixture's *_f64) to 1e-10; in fp32 it is no further from
+    them than a small factor of the reference's own fp32 result.  (One ROI's translation axis nearly cancels: the reference's fp32 value
+    is 1.1e-5 from exact there, so fp32 against fp32 within 1e-6 holds only on a CPU whose kernels sum in the fixture's order.)"""
     g = _load(golden_dir, "axis_head.npz")
+    x, P = G.head_input(), G.head_params("axis")
     with torch.no_grad():
-        rot, tran = oracle.axis_head(G.head_input(), G.head_params("axis"))
+        rot, tran = oracle.axis_head(x, P)
+        rot64, tran64 = oracle.axis_head(x.double(), {k: v.double() if v.is_floating_point() else v for k, v in P.items()})
     np.testing.assert_allclose(rot.numpy(), g["pred_rot_axis"], rtol=1e-5, atol=1e-6)
-    np.testing.assert_allclose(tran.numpy(), g["pred_tran_axis"], rtol=1e-5, atol=1e-6)
+    for key, got, got64 in (("pred_rot_axis", rot, rot64), ("pred_tran_axis", tran, tran64)):
+        truth = g[key + "_f64"]
+        np.testing.assert_allclose(got64.numpy(), truth, rtol=1e-10, atol=1e-12)
+        err, ref_err = float(np.abs(got.numpy() - truth).max()), float(np.abs(g[key] - truth).max())
+        assert err < 8 * ref_err + 2e-6, (key, err, ref_err)
 
 
 def test_depth_head_matches_reference(oracle, golden_dir):

@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 REPS=${REPS:-2}
 for r in $(seq $REPS); do
   for cfg in "$@"; do
-    env $cfg python3 bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-alt-modes --no-operating-points ${BENCH_ARGS:-} 2>/dev/null | python3 -c "
+    env $cfg python3 bench.py --full --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-alt-modes --no-operating-points ${BENCH_ARGS:-} 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d['roofline']['all_conv_kernels']

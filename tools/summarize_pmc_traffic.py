@@ -94,7 +94,7 @@ def main():
         a = ra["algorithmic"]
         ra["per_step_fetch_bytes"], ra["per_step_write_bytes"] = round(tot_f), round(tot_w)
         ra["over_fetch_vs_distinct_cells"] = round(tot_f / a["read_bytes_upper_bound_box_pooler"], 2)
-    doc = {"command": sys.argv[7] if len(sys.argv) > 7 else "python3 bench.py --steps %d --warmup 3 --no-cpu-baseline --no-alt-modes --no-operating-points" % steps,
+    doc = {"command": sys.argv[7] if len(sys.argv) > 7 else "python3 bench.py --full --steps %d --warmup 3 --no-cpu-baseline --no-alt-modes --no-operating-points" % steps,
            "source": "rocprofv3 --kernel-trace (durations), --pmc FETCH_SIZE, --pmc WRITE_SIZE: three separate passes; FETCH_SIZE x2 "
                      "(gfx950 wide-read correction), KiB -> bytes; Infinity-Cache hits are counted as traffic",
            "bench_value": bench["value"], "ms_per_step": bench["ms_per_step"], "kernels": res}
