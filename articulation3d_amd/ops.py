@@ -719,13 +719,23 @@ class _amax_rows:
         self.shape = (e - s,)
 
 
+def _check_res(res: torch.Tensor, B: int, Ho: int, Wo: int, cols: int, res_ups: bool) -> None:
+    """The epilogue reads the residual as [B, Ho, Wo, cols] rows of the GEMM grid (res_ups: [B, Ho/2, Wo/2, cols], row (oh/2, ow/2);
+    csrc/conv_common.h out_rows): any other shape is read as if it were that one, so it is refused before the launch."""
+    _req(res)
+    want = (B, Ho >> 1, Wo >> 1, cols) if res_ups else (B, Ho, Wo, cols)
+    if tuple(res.shape) != want or (res_ups and (Ho % 2 or Wo % 2)):
+        raise ValueError(f"residual of shape {tuple(res.shape)} for an output grid [{B}, {Ho}, {Wo}, {cols}]{' (res_ups)' if res_ups else ''}: expected {want}")
+
+
 def _conv2d_launch(x: torch.Tensor, p: PackedConv, *, x2: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
                    res_ups: bool = False, ups: bool = False, act: Optional[int] = None, splitk: int = 1,
                    m_dev: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, tune: int = 0,
                    wino: Optional[bool] = None, gate: Optional[torch.Tensor] = None, precision=None, dot=None) -> torch.Tensor:
+    global _LAST_PRECISION
     _req(x)
     # Launch plans.  For a module-cached layer called the way the detector calls it (no options, output allocated here) everything in the
-    # descriptor but six tensor pointers is a function of (layer, input shape, residual form, arithmetic mode): the finished descriptor is
+    # descriptor but six tensor pointers is a function of (layer, input shape, residual shape and form, arithmetic mode): the finished descriptor is
     # kept on the PackedConv and later calls write the pointers into a copy -- ~15 -> ~6 us of host time per launch.  The reference's
     # per-frame loop makes ~100 such calls per frame and its single-frame pass is as long on the host as on the GPU (MEASUREMENTS.md,
     # round 6, item 12).  Anything else takes the full path below, which is also what creates the plan.
@@ -733,7 +743,7 @@ def _conv2d_launch(x: torch.Tensor, p: PackedConv, *, x2: Optional[torch.Tensor]
     if (LAUNCH_PLANS and CONV_TIMING is None and x2 is None and m_dev is None and out is None and gate is None and dot is None and not ups and splitk == 1
             and tune == 0 and wino is None and precision is None and act is None and not (p.phase or p.pixshuf or p.stem) and p.presplit
             and (_WINO_SHARE is None or x.data_ptr() not in _WINO_SHARE)):
-        plan_key = (x.shape, res is not None, bool(res_ups), DEFAULT_PRECISION, p.pin_precision, WINO_PLANE_SPLIT, WINO_TUNE, WINO_MAX_HW, BF16_SPLITK_AUTO,
+        plan_key = (x.shape, None if res is None else tuple(res.shape), bool(res_ups), DEFAULT_PRECISION, p.pin_precision, WINO_PLANE_SPLIT, WINO_TUNE, WINO_MAX_HW, BF16_SPLITK_AUTO,
                     x.device, p.w.data_ptr())
         plans = p.__dict__.get("_plans")
         plan = plans.get(plan_key) if plans else None
@@ -743,7 +753,8 @@ def _conv2d_launch(x: torch.Tensor, p: PackedConv, *, x2: Optional[torch.Tensor]
             d = _lib.ConvDesc.from_buffer_copy(proto)
             d.x, d.y = x.data_ptr(), out.data_ptr()
             if res is not None:
-                d.res = _req(res).data_ptr()
+                _check_res(res, oshape[0], d.Ho, d.Wo, d.Cout, res_ups)
+                d.res = res.data_ptr()
             if need_in:
                 d.in_amax = amax_of(x).data_ptr()
             if need_y:
@@ -755,7 +766,6 @@ def _conv2d_launch(x: torch.Tensor, p: PackedConv, *, x2: Optional[torch.Tensor]
             if m_n:
                 wino_m = torch.empty(m_n, device=x.device, dtype=torch.float32)
                 d.wino_m = wino_m.data_ptr()
-            global _LAST_PRECISION
             _LAST_PRECISION = prec
             _lib.check(_lib.lib().a3d_conv2d_nhwc_f32(C.byref(d), _stream()), "a3d_conv2d_nhwc_f32")
             return out
@@ -775,6 +785,8 @@ def _conv2d_launch(x: torch.Tensor, p: PackedConv, *, x2: Optional[torch.Tensor]
         Ho, Wo = H, W
         if p.phase == 5:
             assert precision in (2, 3) and (dot is not None or tuple(out.shape) == (B, 2 * H, 2 * W, p.cols // 4)), "the fused four-phase form belongs to the split-operand arithmetics"
+    if res is not None:
+        _check_res(res, B, Ho, Wo, p.cols, res_ups)
     if out is None:
         shape = (B, 2 * Ho, 2 * Wo, p.cols // 4) if p.pixshuf else (B, Ho, Wo, p.cols)
         out = torch.empty(shape, device=x.device, dtype=torch.float32)

@@ -403,6 +403,42 @@ def test_launch_plans_repeat_the_full_path_bit_for_bit(ops):
         ops.DEFAULT_PRECISION, ops.LAUNCH_PLANS = saved, True
 
 
+def test_launch_plan_refuses_a_residual_of_another_shape(ops):
+    """ADVICE r6 (ops._conv2d_launch): the plan key held only WHETHER a residual came, not its shape, and neither path checked it -- a
+    second call with the same x.shape and a residual of another shape reused the plan and read the new tensor as [B, Ho, Wo, cols].
+    The residual here is deliberately LARGER than the output (2 x cols channels), so that the unfixed launch reads in bounds and merely
+    returns wrong numbers.  Fixed: the call raises before any launch, on the planned path and on the full path, in every arithmetic."""
+    torch.manual_seed(12)
+    B, H, W, Cin, Cout = 2, 30, 40, 256, 256
+    x = torch.relu(torch.randn(B, H, W, Cin, device="cuda"))
+    good = torch.randn(B, H, W, Cout, device="cuda")
+    bad = torch.randn(B, H, W, 2 * Cout, device="cuda")
+    saved = ops.DEFAULT_PRECISION
+    try:
+        for mode in (3, 2, 0):
+            ops.DEFAULT_PRECISION = mode
+            pk = ops.pack_conv(torch.randn(Cout, Cin, 1, 1) / Cin ** 0.5, torch.randn(Cout) * 0.1, None, 1, 0, ops.ACT_RELU)
+            marker = ops.pack_conv(torch.randn(Cout, Cin, 3, 3) / (3 * Cin ** 0.5), None, None, 1, 1, ops.ACT_NONE)
+            ops.conv2d(x[:1].contiguous(), marker)
+            marker_variant = ops.last_conv_variant()
+            y = ops.conv2d(x, pk, res=good)  # full path: creates the plan
+            assert len(pk._plans) == 1
+            assert ops.last_conv_variant() != marker_variant
+            ops.conv2d(x[:1].contiguous(), marker)  # another kernel: its label stays the thread's last one unless a launch follows
+            assert ops.last_conv_variant() == marker_variant
+            with pytest.raises(ValueError, match="residual"):
+                ops.conv2d(x, pk, res=bad)  # same x.shape: the plan's key must not match
+            with pytest.raises(ValueError, match="residual"):
+                ops.conv2d(x, pk, res=bad, act=ops.ACT_RELU)  # an option: the full path checks as well
+            with pytest.raises(ValueError, match="residual"):
+                ops.conv2d(x, pk, res=good[:, ::2, ::2].contiguous())  # the coarser level without res_ups
+            assert len(pk._plans) == 1 and ops.last_conv_variant() == marker_variant  # (nothing was launched)
+            again = ops.conv2d(x, pk, res=good)  # the plan itself is untouched
+            assert torch.equal(again, y)
+    finally:
+        ops.DEFAULT_PRECISION = saved
+
+
 @pytest.mark.parametrize("case", [(4, 120, 160, 64, 256, 64), (5, 119, 161, 64, 256, 64), (16, 60, 80, 128, 512, 128), (15, 59, 81, 128, 512, 128)])
 def test_back_to_back_pointwise_pair_equals_its_two_launches_bit_for_bit(ops, case):
     """Round 6: conv3 + FrozenBN + residual + ReLU of a bottleneck block and conv1 + FrozenBN + ReLU of the next block
