@@ -8,7 +8,6 @@ fp32 NHWC device tensors and only launches kernels through `ops`.
 from __future__ import annotations
 
 import math
-import os
 from typing import Optional
 
 import torch
@@ -57,10 +56,9 @@ def _calibrate_norm(norm, y_raw: torch.Tensor, eps_floor: float = 1e-6):
 
 
 def _publish():
-    """A freshly packed weight set is computed on the CURRENT stream but read afterwards by launches on any stream (1-2 frame batches
-    run one RPN head layer on three streams, the three ROI heads side by side): drain the stream once before the cache is used."""
-    if torch.cuda.is_available() and not os.environ.get("A3D_NO_PUBLISH"):
-        torch.cuda.current_stream().synchronize()
+    """A freshly packed weight set is computed on the current stream but read afterwards by launches on any stream (ops.publish)."""
+    if torch.cuda.is_available():
+        ops.publish()
 
 
 class _Packable(nn.Module):

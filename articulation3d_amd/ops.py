@@ -51,11 +51,6 @@ CONV_TIMING: Optional[list] = None
 DEFAULT_PRECISION = int(os.environ.get("A3D_PRECISION", "3"))
 
 
-def H3_KINDS(p, wino_ok: bool, splitk: int) -> bool:
-    """Layer kinds that have an fp16x2 kernel (the others keep bf16x3 inside mode 3)."""
-    return True  # (Winograd layers whose channel count the wide kernels' 128-wide tiles do not fit -- res2's 64 -> 64 -- run the direct form)
-
-
 def last_conv_variant() -> str:
     """Kernel instantiation dispatched by the calling thread's last conv launch (a3d_last_conv_variant, include/a3d.h):
     the dispatcher's own record, e.g. "conv_pw_kernel<2,2,16> 128x128 persistent"."""
@@ -316,13 +311,19 @@ def amax_reserve(n: int, device) -> None:
         _amax_arena[device] = [torch.zeros(max(_AMAX_CHUNK, n), device=device, dtype=torch.float32), 0]
 
 
+def publish() -> None:
+    """Something made on the CURRENT stream (a packed layer's weights or filter planes, a fresh maxima chunk) is read afterwards by
+    launches on ANY stream (1-2 frame batches run one RPN head layer on three streams, the three ROI heads side by side): drain the
+    stream once, before it is used."""
+    torch.cuda.current_stream().synchronize()
+
+
 def amax_slot(n: int, device) -> torch.Tensor:
     a = _amax_arena.get(device)
     if a is None or a[1] + n > a[0].numel():
         amax_reserve(n, device)
         a = _amax_arena[device]
-        if not os.environ.get("A3D_NO_PUBLISH"):
-            torch.cuda.current_stream().synchronize()  # (an unreserved refill: its fill must be visible to every stream)
+        publish()  # (an unreserved refill: its fill must be visible to every stream)
     t = a[0][a[1]:a[1] + n]
     a[1] += (n + 3) // 4 * 4
     return t
@@ -355,6 +356,112 @@ def _const_amax(t: torch.Tensor, bound: float) -> None:
 
 def _pow2_scale_host(amax: float) -> float:
     return 1.0 if not (amax > 0.0) else 2.0 ** (14 - math.frexp(amax)[1] + 1)
+
+
+def filter_scale(p: PackedConv, wino: bool = False) -> float:
+    """Power-of-two scale of the fp16x2 split of a layer's filter (`_w_scale`; wino: of its Winograd-domain filter, `_u_scale`), made at
+    the first use unless preset (pack_conv_ups_phases gives the four phases of a layer one common scale)."""
+    name = "_u_scale" if wino else "_w_scale"
+    s = getattr(p, name, None)
+    if s is None:
+        s = _pow2_scale_host(float((p.w_wino if wino else p.w).abs().max()))
+        setattr(p, name, s)
+    return s
+
+
+def weight_planes(p: PackedConv, kind: str) -> int:
+    """Device pointer of a packed layer's filter split into planes: kind "w_h2" | "w_x3" = w as two fp16 planes under filter_scale |
+    three exact bf16 planes, [Kpad/16, 2|3, cols, 16]; "w_wino_h2" | "w_wino_x3" = the same of w_wino, [16, Cin/32, 2|3, cols, 32].
+    Made once per packed layer on the current stream and published before its first use: later launches read it from any stream.  A
+    plane already set on the filter's device is used as it is (the trainer presets w_wino_x3)."""
+    wino = kind.startswith("w_wino")
+    src = p.w_wino if wino else p.w
+    t = getattr(p, kind)
+    if t is not None and t.device == src.device:
+        return t.data_ptr()
+    h2 = kind.endswith("h2")
+    n, rows, k, c = (16, src.shape[1], src.shape[2], 32) if wino else (1, src.shape[0], p.Kpad, 16)
+    t = torch.empty(((16,) if wino else ()) + (k // c, 2 if h2 else 3, rows, c), device=src.device, dtype=torch.float16 if h2 else torch.bfloat16)
+    L = _lib.lib()
+    if h2:
+        _lib.check(L.a3d_split_f16x2_chunk(src.data_ptr(), t.data_ptr(), n, rows, k, c, filter_scale(p, wino), _stream()), "a3d_split_f16x2_chunk")
+    elif wino:
+        _lib.check(L.a3d_split_bf16x3(src.data_ptr(), t.data_ptr(), 16, rows, k, _stream()), "a3d_split_bf16x3")
+    else:
+        _lib.check(L.a3d_split_bf16x3_chunk(src.data_ptr(), t.data_ptr(), 1, rows, k, 16, _stream()), "a3d_split_bf16x3_chunk")
+    setattr(p, kind, t)
+    publish()
+    return t.data_ptr()
+
+
+def _conv_desc(p: PackedConv, B: int, H: int, W: int, Cin: int, Cin2: int, Ho: int, Wo: int, act: Optional[int] = None,
+               res_ups: bool = False) -> "_lib.ConvDesc":
+    """A descriptor with the fields every conv entry point fills alike: the layer's filter, epilogue and geometry and one launch's
+    shapes.  The entry point adds the tensors and whatever else is its own."""
+    d = _lib.ConvDesc()
+    d.w, d.scale, d.shift = _p(p.w), _p(p.scale), _p(p.shift)
+    d.B, d.H, d.W, d.Cin, d.Cin2 = B, H, W, Cin, Cin2
+    d.Ho, d.Wo, d.Cout = Ho, Wo, p.cols
+    d.KH, d.KW, d.stride, d.pad = p.KH, p.KW, p.stride, p.pad
+    d.Kpad, d.act = p.Kpad, p.act if act is None else act
+    d.res_ups, d.pixshuf, d.stem, d.phase, d.splitk = int(res_ups), int(p.pixshuf), int(p.stem), int(p.phase), 1
+    return d
+
+
+def _y_amax(out: torch.Tensor) -> int:
+    """Device pointer of the slot into which a launch's epilogue records the per-image maxima of `out`: the slot `out` already carries
+    (the four phase launches of an upsampled conv share their output), or a new one."""
+    ya = getattr(out, "_a3d_amax", None)
+    if ya is None or ya.numel() != out.shape[0]:
+        ya = out._a3d_amax = amax_slot(out.shape[0], out.device)
+    return ya.data_ptr()
+
+
+def _image_blocks(B: int, nb: int, *ts):
+    """Blocks [s, e) of at most nb images, for batches past the 32-bit offsets of one launch (every image's result is a function of that
+    image alone, so the blocks reproduce the single launch bit for bit); yields (s, e, [each tensor of ts cut to the block, keeping its
+    rows of the recorded maxima]).  None stays None; a block of the whole batch is the tensors themselves."""
+    for s in range(0, B, nb):
+        e = min(s + nb, B)
+        yield s, e, [t if t is None or e - s == B else keep_amax(t[s:e], _amax_rows(t, s, e)) for t in ts]
+
+
+# CONV_TIMING_ONLY (a set of variant labels): event pairs only around the launches whose label is in the set; every other launch goes
+# out as if nothing were measured (700 event pairs per 64-frame step cost 0.8 ms of its 44).  A label that only the dispatcher knows
+# (last_conv_variant) is the one the same memo key launched when it was last timed; a key seen for the first time is timed.
+CONV_TIMING_ONLY: Optional[frozenset] = None
+_TIMED_VARIANTS: dict = {}
+_ERR_UNSUPPORTED = -3  # A3D_ERR_UNSUPPORTED
+
+
+def _launch(fn, *args, precision: Optional[int] = None, rec=None, unsupported: bool = False) -> bool:
+    """fn(*args, current stream), one call of the kernel library, checked.  precision: a3d_conv_desc.precision of a conv launch, kept for
+    the precision audit (_LAST_PRECISION).  rec() -> (label or None for the dispatcher's own, algorithmic flops, shape, executed flops,
+    pipe, memo key): under CONV_TIMING the call is bracketed by HIP events on the launch stream and the record (label, flops, start, end,
+    shape, executed flops, pipe, stream) is appended.  unsupported: A3D_ERR_UNSUPPORTED is an answer (returns False), not an error."""
+    global _LAST_PRECISION
+    if precision is not None:
+        _LAST_PRECISION = precision
+    timed = CONV_TIMING is not None and rec is not None
+    if timed:
+        label, fl, shape, ex, pipe, key = rec()
+        if CONV_TIMING_ONLY is not None:
+            known = label if label is not None else _TIMED_VARIANTS.get(key)
+            timed = known is None or known in CONV_TIMING_ONLY
+        if timed:
+            e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+            e0.record()
+    rc = fn(*args, _stream())
+    if rc:
+        if unsupported and rc == _ERR_UNSUPPORTED:
+            return False
+        _lib.check(rc, fn.__name__)
+    if timed:
+        e1.record()
+        if label is None:
+            label = _TIMED_VARIANTS[key] = last_conv_variant()
+        CONV_TIMING.append((label, fl, e0, e1, shape, ex, pipe, _stream()))
+    return True
 
 
 _WINO_SHARE: Optional[dict] = None
@@ -407,60 +514,36 @@ def conv2d_levels(xs: Sequence[torch.Tensor], p: PackedConv) -> list:
     if not ok or total * p.Cin * 4 > _ADDR_LIMIT:
         return [conv2d(x, p) for x in xs]
     dev = xs[0].device
-    if getattr(p, "_u_scale", None) is None:
-        p._u_scale = _pow2_scale_host(float(p.w_wino.abs().max()))
-    if p.w_wino_h2 is None or p.w_wino_h2.device != p.w_wino.device:
-        rows, cols = p.w_wino.shape[1], p.w_wino.shape[2]
-        p.w_wino_h2 = torch.empty((16, cols // 32, 2, rows, 32), device=p.w_wino.device, dtype=torch.float16)
-        _lib.check(_lib.lib().a3d_split_f16x2_chunk(p.w_wino.data_ptr(), p.w_wino_h2.data_ptr(), 16, rows, cols, 32, p._u_scale, _stream()), "a3d_split_f16x2_chunk")
-        if not os.environ.get("A3D_NO_PUBLISH"):
-            torch.cuda.current_stream().synchronize()
+    w_h2, u_scale = weight_planes(p, "w_wino_h2"), filter_scale(p, wino=True)
     ws = torch.empty(16 * total * p.Cin, device=dev, dtype=torch.float32)
     descs = (_lib.ConvDesc * len(xs))()
     outs, off = [], 0
-    global _LAST_PRECISION
-    _LAST_PRECISION = 3
-    # measurement (bench.py): event pairs around the transforms and around the one GEMM launch, under the same rule as _conv2d_launch
-    label = "wino_gemm_h2w_kernel<4>"  # (the same kernel as a single map's launch -- the table in its epilogue has five rows instead of one)
-    timing = CONV_TIMING is not None and (CONV_TIMING_ONLY is None or label in CONV_TIMING_ONLY or "wino_input_kernel" in CONV_TIMING_ONLY)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing else None
-    if timing:
-        ev[0].record()
+    shape = lambda: f"{xs[0].shape[0]}x[{'+'.join(str(x.shape[1]) + 'x' + str(x.shape[2]) for x in xs)}]x{p.Cin}->{p.cols} k3 s1"
     for k, x in enumerate(xs):
         _req(x)
         B, H, W, Cin = x.shape
         out = torch.empty((B, H, W, p.cols), device=dev, dtype=torch.float32)
+        descs[k] = _conv_desc(p, B, H, W, Cin, 0, H, W)
         d = descs[k]
-        d.x, d.w, d.scale, d.shift, d.y = _p(x), _p(p.w), _p(p.scale), _p(p.shift), _p(out)
-        d.B, d.H, d.W, d.Cin, d.Cin2 = B, H, W, Cin, 0
-        d.Ho, d.Wo, d.Cout = H, W, p.cols
-        d.KH, d.KW, d.stride, d.pad = 3, 3, 1, 1
-        d.Kpad, d.ups, d.act = p.Kpad, 0, p.act
-        d.res_ups, d.pixshuf, d.stem, d.splitk = 0, 0, 0, 1
-        d.tune, d.phase, d.precision = 0, 0, 3
-        d.w_wino, d.w_wino_x3, d.w_scale = p.w_wino.data_ptr(), p.w_wino_h2.data_ptr(), p._u_scale
+        d.x, d.y, d.precision = _p(x), _p(out), 3
+        d.w_wino, d.w_wino_x3, d.w_scale = p.w_wino.data_ptr(), w_h2, u_scale
         d.in_amax = amax_of(x).data_ptr()
-        if not os.environ.get("A3D_NO_YAMAX"):
-            out._a3d_amax = amax_slot(B, dev)
-            d.y_amax = out._a3d_amax.data_ptr()
+        d.y_amax = _y_amax(out)
         d.workspace = ws.data_ptr()
         d.wino_t_off, d.wino_t_total = off, total
-        _lib.check(_lib.lib().a3d_wino_input_transform(C.byref(d), _stream()), "a3d_wino_input_transform")
+        _launch(_lib.lib().a3d_wino_input_transform, C.byref(d), precision=3, rec=lambda: ("wino_input_kernel", 0.0, shape(), 0.0, "none", None))
         if _WINO_SHARE is not None:
             ent = _WINO_SHARE.get(x.data_ptr())
             if ent is not None and ent[0].shape == x.shape:
                 ent[1:] = [ws, 3, (off, total)]  # [tensor, V buffer, arithmetic of its format, (slice offset, tiles per run)]
         off += tiles[k]
         outs.append(out)
-    if timing:
-        ev[1].record()
-    _lib.check(_lib.lib().a3d_wino_gemm_levels(descs, len(xs), _stream()), "a3d_wino_gemm_levels")
-    if timing:
-        ev[2].record()
+
+    def rec():  # (the same kernel as a single map's launch -- the table in its epilogue has five rows instead of one)
         px = sum(x.shape[0] * x.shape[1] * x.shape[2] for x in xs)
-        shape = f"{xs[0].shape[0]}x[{'+'.join(str(x.shape[1]) + 'x' + str(x.shape[2]) for x in xs)}]x{p.Cin}->{p.cols} k3 s1"
-        CONV_TIMING.append(("wino_input_kernel", 0.0, ev[0], ev[1], shape, 0.0, "none", _stream()))
-        CONV_TIMING.append((label, 2.0 * px * p.cols * 9 * p.Cin, ev[1], ev[2], shape, 2.0 * total * 16 * p.cols * p.Cin, "f16x3", _stream()))
+        return "wino_gemm_h2w_kernel<4>", 2.0 * px * p.cols * 9 * p.Cin, shape(), 2.0 * total * 16 * p.cols * p.Cin, "f16x3", None
+
+    _launch(_lib.lib().a3d_wino_gemm_levels, descs, len(xs), precision=3, rec=rec)
     return outs
 
 
@@ -514,16 +597,14 @@ def _conv2d_blocks(x, p, nb, hw_out, *, x2, res, out, gate, m_dev, **kw):
     if out is None:
         shape = (B, 2 * Ho, 2 * Wo, p.cols // 4) if p.pixshuf else (B, Ho, Wo, p.cols)
         out = torch.empty(shape, device=x.device, dtype=torch.float32)
-    cut = lambda t, s, e: None if t is None else keep_amax(t[s:e], _amax_rows(t, s, e))
     recorded = []
-    for s in range(0, B, nb):
-        e = min(s + nb, B)
+    for s, e, (xb, x2b, rb, gb) in _image_blocks(B, nb, x, x2, res, gate):
         md = None if m_dev is None else (m_dev.reshape(1) - s).clamp(0, e - s).to(torch.int32)  # live rows of this block (device side)
         o = out[s:e]
         ya = getattr(out, "_a3d_amax", None)
         if ya is not None and ya.numel() == B:  # (the phase launches of an upsampled conv share their output's slots)
             o._a3d_amax = ya[s:e]
-        _conv2d_launch(cut(x, s, e), p, x2=cut(x2, s, e), res=cut(res, s, e), out=o, gate=cut(gate, s, e), m_dev=md, **kw)
+        _conv2d_launch(xb, p, x2=x2b, res=rb, out=o, gate=gb, m_dev=md, **kw)
         recorded.append(getattr(o, "_a3d_amax", None))
     if getattr(out, "_a3d_amax", None) is None and all(r is not None for r in recorded):
         out._a3d_amax = torch.cat(recorded)
@@ -581,13 +662,7 @@ def _conv2d_bf16_storage(x, p: PackedConv, *, res, res_ups, act, out, gate, prec
            x.dtype, out.dtype, None if res is None else res.dtype, None if gate is None else gate.dtype, bool(res_ups), int(tune), BF16_SPLITK_AUTO, BF16_SPLITK)
     proto = _BF16_DESC_CACHE.get(key)
     if proto is None:
-        d = _lib.ConvDesc()
-        d.w, d.scale, d.shift = _p(p.w), _p(p.scale), _p(p.shift)
-        d.B, d.H, d.W, d.Cin, d.Cin2 = B, H, W, Cin, 0
-        d.Ho, d.Wo, d.Cout = Ho, Wo, p.cols
-        d.KH, d.KW, d.stride, d.pad = p.KH, p.KW, p.stride, p.pad
-        d.Kpad, d.ups, d.act = p.Kpad, 0, act_eff
-        d.res_ups, d.pixshuf, d.stem, d.splitk = int(res_ups), 0, 0, 1
+        d = _conv_desc(p, B, H, W, Cin, 0, Ho, Wo, act=act_eff, res_ups=res_ups)
         d.precision = 1
         b16 = lambda t: t is not None and t.dtype == torch.bfloat16
         d.io_bf16 = (1 if b16(x) else 0) | (2 if b16(out) else 0) | (4 if b16(res) else 0) | (8 if b16(gate) else 0)
@@ -609,15 +684,12 @@ def _conv2d_bf16_storage(x, p: PackedConv, *, res, res_ups, act, out, gate, prec
     if sk > 1:
         ws = torch.empty(sk * B * Ho * Wo * p.cols, device=x.device, dtype=torch.float32)
         d.workspace = ws.data_ptr()
-    if CONV_TIMING is not None:  # (tools/train_bench.py's roofline leg: these launches carry most of the bf16 step's FLOPs)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _lib.check(_lib.lib().a3d_conv2d_nhwc_f32(C.byref(d), _stream()), "a3d_conv2d_nhwc_f32")
-        e1.record()
+
+    def rec():  # (tools/train_bench.py's roofline leg: these launches carry most of the bf16 step's FLOPs)
         fl = 2.0 * B * Ho * Wo * p.cols * p.KH * p.KW * p.Cin
-        CONV_TIMING.append((last_conv_variant(), fl, e0, e1, f"{B}x{H}x{W}x{Cin}->{p.cols} k{p.KH} s{p.stride} io{int(d.io_bf16)}", fl, "bf16", _stream()))
-        return out
-    _lib.check(_lib.lib().a3d_conv2d_nhwc_f32(C.byref(d), _stream()), "a3d_conv2d_nhwc_f32")
+        return None, fl, f"{B}x{H}x{W}x{Cin}->{p.cols} k{p.KH} s{p.stride} io{int(d.io_bf16)}", fl, "bf16", key
+
+    _launch(_lib.lib().a3d_conv2d_nhwc_f32, C.byref(d), precision=1, rec=rec)
     return out
 
 
@@ -641,7 +713,7 @@ def presplit_f16x2(x: torch.Tensor, x2: Optional[torch.Tensor] = None):
 def _conv2d_presplit(x, p: PackedConv, *, x2=None, res=None, res_ups=False, act=None, out=None) -> torch.Tensor:
     """A direct fp16x2 layer on PRE-SPLIT activations (x, x2: torch.float16 [B, H, W, C/16, 2, 16] with recorded maxima): the wide kernel
     with both operands by LDS-DMA ("conv_h2w_kernel xd").  Bit-identical to conv2d on the fp32 tensor the planes were split from."""
-    if DEFAULT_PRECISION != 3 and not os.environ.get("A3D_ALLOW_PRESPLIT"):
+    if DEFAULT_PRECISION != 3:
         raise RuntimeError("pre-split activations belong to the fp16x2 arithmetic (A3D_PRECISION=3)")
     ok = lambda t: t.is_cuda and t.is_contiguous() and t.dtype == torch.float16 and t.dim() == 6 and t.shape[4:] == (2, 16)
     if not ok(x) or (x2 is not None and not ok(x2)):
@@ -652,61 +724,32 @@ def _conv2d_presplit(x, p: PackedConv, *, x2=None, res=None, res_ups=False, act=
     assert Cin + Cin2 == p.Cin and not (p.stem or p.pixshuf or p.phase) and p.presplit and p.Kpad == p.KH * p.KW * p.Cin, "plain direct layers only"
     Ho = (H + 2 * p.pad - p.KH) // p.stride + 1
     Wo = (W + 2 * p.pad - p.KW) // p.stride + 1
-    if B * max(H * W * max(Cin, Cin2), Ho * Wo * p.cols) * 4 > _ADDR_LIMIT:
-        # (blocks of images, as conv2d does for fp32 tensors: every image's result is a function of that image alone)
-        nb = max(1, _ADDR_LIMIT // (max(H * W * max(Cin, Cin2), Ho * Wo * p.cols) * 4))
-        if out is None:
-            out = torch.empty((B, Ho, Wo, p.cols), device=x.device, dtype=torch.float32)
-        ya = amax_slot(B, x.device)
-        cut = lambda t, s0, e0: None if t is None else keep_amax(t[s0:e0], _amax_rows(t, s0, e0))
-        for s0 in range(0, B, nb):
-            e0 = min(s0 + nb, B)
-            o = out[s0:e0]
-            o._a3d_amax = ya[s0:e0]
-            _conv2d_presplit(cut(x, s0, e0), p, x2=cut(x2, s0, e0), res=cut(res, s0, e0), res_ups=res_ups, act=act, out=o)
-        out._a3d_amax = ya
-        return out
     if out is None:
         out = torch.empty((B, Ho, Wo, p.cols), device=x.device, dtype=torch.float32)
-    d = _lib.ConvDesc()
-    d.x_h2, d.x2_h2 = x.data_ptr(), _p(x2)
-    d.w, d.scale, d.shift, d.res, d.y = _p(p.w), _p(p.scale), _p(p.shift), _p(res), _p(out)
-    d.B, d.H, d.W, d.Cin, d.Cin2 = B, H, W, Cin, Cin2
-    d.Ho, d.Wo, d.Cout = Ho, Wo, p.cols
-    d.KH, d.KW, d.stride, d.pad = p.KH, p.KW, p.stride, p.pad
-    d.Kpad, d.ups, d.act = p.Kpad, 0, p.act if act is None else act
-    d.res_ups, d.pixshuf, d.stem, d.splitk = int(res_ups), 0, 0, 1
-    d.precision = 3
-    d.tune = int(os.environ.get("A3D_XD_TUNE", "0"))  # (developer builds with -DA3D_ABLATIONS only: timing-only variants of the ring)
+    per_image = max(H * W * max(Cin, Cin2), Ho * Wo * p.cols) * 4
+    if B * per_image > _ADDR_LIMIT:  # (blocks of images, as conv2d does for fp32 tensors)
+        ya = out._a3d_amax = amax_slot(B, x.device)
+        for s, e, (xb, x2b, rb) in _image_blocks(B, max(1, _ADDR_LIMIT // per_image), x, x2, res):
+            o = out[s:e]
+            o._a3d_amax = ya[s:e]
+            _conv2d_presplit(xb, p, x2=x2b, res=rb, res_ups=res_ups, act=act, out=o)
+        return out
     a = getattr(x, "_a3d_amax", None)
     if a is None or a.numel() != B:
         raise RuntimeError("a pre-split tensor carries the per-image maxima it was scaled by (_a3d_amax)")
+    d = _conv_desc(p, B, H, W, Cin, Cin2, Ho, Wo, act=act, res_ups=res_ups)
+    d.x_h2, d.x2_h2, d.res, d.y = x.data_ptr(), _p(x2), _p(res), out.data_ptr()
+    d.precision = 3
+    d.tune = int(os.environ.get("A3D_XD_TUNE", "0"))  # (developer builds with -DA3D_ABLATIONS only: timing-only variants of the ring)
     d.in_amax = a.data_ptr()  # (two sources: both were split under the shared maximum, recorded on each)
-    if getattr(p, "_w_scale", None) is None:
-        p._w_scale = _pow2_scale_host(float(p.w.abs().max()))
-    d.w_scale = p._w_scale
-    if p.w_h2 is None or p.w_h2.device != p.w.device:
-        p.w_h2 = torch.empty((p.Kpad // 16, 2, p.w.shape[0], 16), device=p.w.device, dtype=torch.float16)
-        _lib.check(_lib.lib().a3d_split_f16x2_chunk(p.w.data_ptr(), p.w_h2.data_ptr(), 1, p.w.shape[0], p.Kpad, 16, d.w_scale, _stream()), "a3d_split_f16x2_chunk")
-        if not os.environ.get("A3D_NO_PUBLISH"):
-            torch.cuda.current_stream().synchronize()
-    d.w_x3 = p.w_h2.data_ptr()
-    if not os.environ.get("A3D_NO_YAMAX"):
-        ya = getattr(out, "_a3d_amax", None)
-        if ya is None or ya.numel() != out.shape[0]:
-            ya = out._a3d_amax = amax_slot(out.shape[0], out.device)
-        d.y_amax = ya.data_ptr()
-    timing = CONV_TIMING is not None
-    if timing and CONV_TIMING_ONLY is not None:
-        timing = "conv_h2w_kernel xd" in CONV_TIMING_ONLY
-    if timing:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.lib().a3d_conv2d_nhwc_f32(C.byref(d), _stream()), "a3d_conv2d_nhwc_f32")
-    if timing:
-        e1.record()
+    d.w_scale, d.w_x3 = filter_scale(p), weight_planes(p, "w_h2")
+    d.y_amax = _y_amax(out)
+
+    def rec():
         fl = 2.0 * B * Ho * Wo * p.cols * p.KH * p.KW * p.Cin
-        CONV_TIMING.append((last_conv_variant(), fl, e0, e1, f"{B}x{H}x{W}x{Cin + Cin2}->{p.cols} k{p.KH} s{p.stride} presplit", fl, "f16x3", _stream()))
+        return None, fl, f"{B}x{H}x{W}x{Cin + Cin2}->{p.cols} k{p.KH} s{p.stride} presplit", fl, "f16x3", (id(p), B, H, W, Cin, Cin2, "presplit")
+
+    _launch(_lib.lib().a3d_conv2d_nhwc_f32, C.byref(d), precision=3, rec=rec)
     return out
 
 
@@ -728,11 +771,61 @@ def _check_res(res: torch.Tensor, B: int, Ho: int, Wo: int, cols: int, res_ups: 
         raise ValueError(f"residual of shape {tuple(res.shape)} for an output grid [{B}, {Ho}, {Wo}, {cols}]{' (res_ups)' if res_ups else ''}: expected {want}")
 
 
+_PIPE = {0: "f32", 1: "bf16", 2: "bf16x6", 3: "f16x3"}  # (CONV_TIMING's pipe of each a3d_conv_desc.precision)
+
+
+def _arithmetic(p: PackedConv, default: int, wino_tune: int, precision, Cin: int, Cin2: int, *, ups: bool, splitk: int, tune: int, wino,
+                x2: bool, res: bool, gate: bool, m_dev: bool) -> Tuple[int, bool, int]:
+    """(a3d_conv_desc.precision, Winograd form or not, a3d_conv_desc.tune) of a _conv2d_launch call, from the layer's fields, the call's
+    options (precision: None = the module's `default` arithmetic, "bf16x3" = that mode, an int = that arithmetic; x2 ... m_dev: whether
+    the call passes them) and WINO_TUNE.  A function of the layer and the options only, never of the batch (batch-size invariance)."""
+    wino_ok = (p.w_wino is not None and not res and splitk == 1 and not m_dev and (tune in (0, 7, 8, 23, 24, 25) or tune >= 200) and not ups
+               and (wino if wino is not None else True))
+    if precision is None or precision == "bf16x3":  # a MODE (module default, or the caller's "bf16x3"): pick per layer kind
+        mode = default if precision is None else 2
+        if mode == 3 and p.pin_precision == 2:  # pinned by the precision audit (a function of the LAYER: batch invariance survives)
+            mode = 2
+        plain = not (p.stem or ups or p.phase or p.pixshuf or x2 or splitk != 1 or m_dev) and p.Kpad == p.KH * p.KW * p.Cin
+        if mode == 1:
+            precision = 1 if plain and p.Cin % 32 == 0 else 0
+        elif mode in (2, 3):
+            # (the bf16x3 kernel also takes the phase convs of the depth decoder and their 2-source channel concat)
+            # (split-K -- the 50176-deep head FCs -- only through the wide kernel, whose conditions the last line repeats)
+            x3_ok = p.stem and not ups and splitk == 1 and not m_dev and not x2 and not res
+            x3_ok = x3_ok or (not (p.stem or ups or m_dev) and p.Kpad == p.KH * p.KW * p.Cin
+                     and not (p.pixshuf and (res or gate))
+                     and (splitk == 1 or (p.presplit and p.Kpad >= 4096 and p.cols >= 192 and -(-p.cols // 256) * 256 <= p.cols + p.cols // 4
+                                          and not p.phase and not gate and not p.pixshuf))
+                     and (not x2 or Cin2 == Cin) and Cin % 16 == 0 and not (p.phase and res))
+            # Winograd layers keep the Winograd form with the split-operand GEMM (conv_wino.hip 2x, 32-deep chunks).
+            # (Measured and NOT taken: the 64-channel 3x3 layers of res2 are 0.18 ms faster each in the one-launch fp32 Winograd
+            # kernel -- 986 vs 971 frames/s -- but with that mix one of the 800 scores of the end-to-end test at threshold 0.0 moved
+            # to 1.007e-4 from the oracle's, past the stated 1e-4: the arithmetic stays uniform.)
+            precision = 2 if tune == 0 and ((x3_ok and not wino_ok) or (wino_ok and (Cin + Cin2) % 32 == 0)) else 0
+            if precision == 2 and mode == 3:
+                precision = 3
+        else:
+            precision = 0
+    # Winograd F(2x2,3x3) for every 3x3 s1 p1 layer that has Winograd-domain weights.  The choice must not depend on the
+    # batch / ROI count (a frame's result would otherwise depend on how it was batched), so it is a function of the layer
+    # only; measured faster than the direct form down to the 8x10 level (tools/conv_bench.py: res5 0.50 -> 0.30 ms,
+    # p5 RPN conv 0.18 -> 0.10 ms, res2 64->64 0.40 -> 0.38 ms per 32 frames).  `wino=False` forces the direct form.
+    use_wino = wino_ok and (precision == 0 or (precision in (2, 3) and tune in (0, 8, 23, 24, 25) and (Cin + Cin2) % 32 == 0))
+    if use_wino and precision == 3 and (-(-p.cols // 64) % 2 or (Cin + Cin2 < 256 and wino is None)):
+        # fp16x2: the direct form where the wide Winograd kernels' 128-channel tiles do not fit (res2's 64 -> 64) and for layers under
+        # 256 input channels -- with three MFMAs per k step the 16-plane round trip costs more than the 2.25x multiply-adds it saves
+        # (whole-layer times at 64 frames, tools/h2_wino_vs_direct.py: 60x80x128 -> 128 0.435 Winograd | 0.352 direct; p2 256 -> 256
+        # 3.99 | 4.85).  A function of the layer only.
+        use_wino = False
+    if use_wino and precision == 3 and tune == 0 and wino_tune:
+        tune = wino_tune
+    return int(precision), use_wino, int(tune)
+
+
 def _conv2d_launch(x: torch.Tensor, p: PackedConv, *, x2: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
                    res_ups: bool = False, ups: bool = False, act: Optional[int] = None, splitk: int = 1,
                    m_dev: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, tune: int = 0,
                    wino: Optional[bool] = None, gate: Optional[torch.Tensor] = None, precision=None, dot=None) -> torch.Tensor:
-    global _LAST_PRECISION
     _req(x)
     # Launch plans.  For a module-cached layer called the way the detector calls it (no options, output allocated here) everything in the
     # descriptor but six tensor pointers is a function of (layer, input shape, residual shape and form, arithmetic mode): the finished descriptor is
@@ -743,8 +836,10 @@ def _conv2d_launch(x: torch.Tensor, p: PackedConv, *, x2: Optional[torch.Tensor]
     if (LAUNCH_PLANS and CONV_TIMING is None and x2 is None and m_dev is None and out is None and gate is None and dot is None and not ups and splitk == 1
             and tune == 0 and wino is None and precision is None and act is None and not (p.phase or p.pixshuf or p.stem) and p.presplit
             and (_WINO_SHARE is None or x.data_ptr() not in _WINO_SHARE)):
-        plan_key = (x.shape, None if res is None else tuple(res.shape), bool(res_ups), DEFAULT_PRECISION, p.pin_precision, WINO_PLANE_SPLIT, WINO_TUNE, WINO_MAX_HW, BF16_SPLITK_AUTO,
-                    x.device, p.w.data_ptr())
+        # The key: what _arithmetic reads that such a call leaves free (the module default, WINO_TUNE, the layer's pin; its other inputs are
+        # fixed above or by the layer), the shapes, and the module switches the rest of the descriptor reads.
+        plan_key = (DEFAULT_PRECISION, WINO_TUNE, p.pin_precision, x.shape, None if res is None else tuple(res.shape), bool(res_ups),
+                    WINO_PLANE_SPLIT, BF16_SPLITK_AUTO, BF16_SPLITK, x.device, p.w.data_ptr())
         plans = p.__dict__.get("_plans")
         plan = plans.get(plan_key) if plans else None
         if plan is not None:
@@ -766,8 +861,7 @@ def _conv2d_launch(x: torch.Tensor, p: PackedConv, *, x2: Optional[torch.Tensor]
             if m_n:
                 wino_m = torch.empty(m_n, device=x.device, dtype=torch.float32)
                 d.wino_m = wino_m.data_ptr()
-            _LAST_PRECISION = prec
-            _lib.check(_lib.lib().a3d_conv2d_nhwc_f32(C.byref(d), _stream()), "a3d_conv2d_nhwc_f32")
+            _launch(_lib.lib().a3d_conv2d_nhwc_f32, C.byref(d), precision=prec)
             return out
     B, H, W, Cin = x.shape
     Cin2 = 0
@@ -790,143 +884,57 @@ def _conv2d_launch(x: torch.Tensor, p: PackedConv, *, x2: Optional[torch.Tensor]
     if out is None:
         shape = (B, 2 * Ho, 2 * Wo, p.cols // 4) if p.pixshuf else (B, Ho, Wo, p.cols)
         out = torch.empty(shape, device=x.device, dtype=torch.float32)
-    d = _lib.ConvDesc()
-    d.x, d.x2, d.w, d.scale, d.shift, d.res, d.y = _p(x), _p(x2), _p(p.w), _p(p.scale), _p(p.shift), _p(res), _p(out)
-    d.B, d.H, d.W, d.Cin, d.Cin2 = B, H, W, Cin, Cin2
-    d.Ho, d.Wo, d.Cout = Ho, Wo, p.cols
-    d.KH, d.KW, d.stride, d.pad = p.KH, p.KW, p.stride, p.pad
-    d.Kpad, d.ups, d.act = p.Kpad, int(ups), p.act if act is None else act
-    d.res_ups, d.pixshuf, d.stem, d.splitk = int(res_ups), int(p.pixshuf), int(p.stem), int(splitk)
-    d.m_dev = _p(m_dev)
+    d = _conv_desc(p, B, H, W, Cin, Cin2, Ho, Wo, act=act, res_ups=res_ups)
+    d.x, d.x2, d.res, d.y = _p(x), _p(x2), _p(res), _p(out)
+    d.ups, d.splitk, d.m_dev = int(ups), int(splitk), _p(m_dev)
     if gate is not None:
         assert tuple(_req(gate).shape) == tuple(out.shape), (gate.shape, out.shape)
         d.gate = gate.data_ptr()
-    d.tune = int(tune)
     if dot is not None:  # (phase 5 only: the nine tap products of a following 3x3 convolution to one channel instead of the output)
         assert p.phase == 5 and precision == 3
         d.dot_w, d.dot_y = _req(dot[0]).data_ptr(), _req(dot[1]).data_ptr()
         d.y = None  # (`out` is the tap-product tensor itself, kept as the handle of the recorded maxima: the [B,2H,2W,C] output is never formed)
-    wino_ok = (p.w_wino is not None and res is None and splitk == 1 and m_dev is None and (tune in (0, 7, 8, 23, 24, 25) or tune >= 200) and not ups
-               and (wino if wino is not None else True))
-    if precision is None or precision == "bf16x3":  # a MODE (module default, or the caller's "bf16x3"): pick per layer kind
-        mode = DEFAULT_PRECISION if precision is None else 2
-        if mode == 3 and p.pin_precision == 2:  # pinned by the precision audit (a function of the LAYER: batch invariance survives)
-            mode = 2
-        plain = not (p.stem or ups or p.phase or p.pixshuf or x2 is not None or splitk != 1 or m_dev is not None) and p.Kpad == p.KH * p.KW * p.Cin
-        if mode == 1:
-            precision = 1 if plain and p.Cin % 32 == 0 else 0
-        elif mode in (2, 3):  # a function of the layer only, like the Winograd rule (batch-size invariance)
-            # (the bf16x3 kernel also takes the phase convs of the depth decoder and their 2-source channel concat)
-            # (split-K -- the 50176-deep head FCs -- only through the wide kernel, whose conditions the last line repeats)
-            x3_ok = p.stem and not ups and splitk == 1 and m_dev is None and x2 is None and res is None
-            x3_ok = x3_ok or (not (p.stem or ups or m_dev is not None) and p.Kpad == p.KH * p.KW * p.Cin
-                     and not (p.pixshuf and (res is not None or gate is not None))
-                     and (splitk == 1 or (p.presplit and p.Kpad >= 4096 and p.cols >= 192 and -(-p.cols // 256) * 256 <= p.cols + p.cols // 4
-                                          and not p.phase and gate is None and not p.pixshuf))
-                     and (x2 is None or Cin2 == Cin) and Cin % 16 == 0 and not (p.phase and res is not None))
-            # Winograd layers keep the Winograd form with the split-operand GEMM (conv_wino.hip 2x, 32-deep chunks).
-            # (Measured and NOT taken: the 64-channel 3x3 layers of res2 are 0.18 ms faster each in the one-launch fp32 Winograd
-            # kernel -- 986 vs 971 frames/s -- but with that mix one of the 800 scores of the end-to-end test at threshold 0.0 moved
-            # to 1.007e-4 from the oracle's, past the stated 1e-4: the arithmetic stays uniform.)
-            precision = 2 if tune == 0 and ((x3_ok and not wino_ok) or (wino_ok and (Cin + Cin2) % 32 == 0)) else 0
-            if precision == 2 and mode == 3 and H3_KINDS(p, wino_ok, splitk):
-                precision = 3
-        else:
-            precision = 0
-    d.precision = int(precision)
-    if d.precision == 1 and p.w_b16 is not None:
+    precision, use_wino, tune = _arithmetic(p, DEFAULT_PRECISION, WINO_TUNE, precision, Cin, Cin2, ups=ups, splitk=splitk, tune=tune, wino=wino,
+                                            x2=x2 is not None, res=res is not None, gate=gate is not None, m_dev=m_dev is not None)
+    d.precision, d.tune = precision, tune
+    if precision == 1 and p.w_b16 is not None:
         d.w_bf16 = p.w_b16.data_ptr()
-    if (d.precision == 1 and splitk == 1 and BF16_SPLITK_AUTO and not (p.stem or ups or p.phase or p.pixshuf or x2 is not None or m_dev is not None or res_ups)
+    if (precision == 1 and splitk == 1 and BF16_SPLITK_AUTO and not (p.stem or ups or p.phase or p.pixshuf or x2 is not None or m_dev is not None or res_ups)
             and p.Kpad == p.KH * p.KW * p.Cin and p.Cin % 32 == 0):
         splitk = _bf16_splitk(B * Ho * Wo, p.cols, p.Kpad)  # (bf16 arithmetic: small grids with long reductions)
         d.splitk = splitk
-    _LAST_PRECISION = int(precision)
-    d.phase = int(p.phase)
-    if d.precision == 3:  # fp16x2: per-image scales of the activations (recorded by their producers), one static scale of the filter
+    if precision == 3:  # fp16x2: per-image scales of the activations (recorded by their producers), one static scale of the filter
         d.in_amax = amax_of(x).data_ptr()
         if x2 is not None:
             d.in_amax2 = amax_of(x2).data_ptr()
-        if getattr(p, "_w_scale", None) is None:
-            p._w_scale = _pow2_scale_host(float(p.w.abs().max()))
-        d.w_scale = p._w_scale
-    if d.precision in (2, 3) and (DEFAULT_PRECISION == 3 or d.precision == 3) and not p.pixshuf and not os.environ.get("A3D_NO_YAMAX"):
-        ya = getattr(out, "_a3d_amax", None)  # (the four phase launches of an upsampled conv share their output and its slot)
-        if ya is None or ya.numel() != out.shape[0]:
-            ya = out._a3d_amax = amax_slot(out.shape[0], out.device)
-        d.y_amax = ya.data_ptr()
-    # Winograd F(2x2,3x3) for every 3x3 s1 p1 layer that has Winograd-domain weights.  The choice must not depend on the
-    # batch / ROI count (a frame's result would otherwise depend on how it was batched), so it is a function of the layer
-    # only; measured faster than the direct form down to the 8x10 level (tools/conv_bench.py: res5 0.50 -> 0.30 ms,
-    # p5 RPN conv 0.18 -> 0.10 ms, res2 64->64 0.40 -> 0.38 ms per 32 frames).  `wino=False` forces the direct form.
-    use_wino = wino_ok and (precision == 0 or (precision in (2, 3) and tune in (0, 8, 23, 24, 25) and (Cin + Cin2) % 32 == 0))
-    if use_wino and precision == 3 and (-(-p.cols // 64) % 2 or (Cin + Cin2 < 256 and wino is None)):
-        # fp16x2: the direct form where the wide Winograd kernels' 128-channel tiles do not fit (res2's 64 -> 64) and for layers under
-        # 256 input channels -- with three MFMAs per k step the 16-plane round trip costs more than the 2.25x multiply-adds it saves
-        # (whole-layer times at 64 frames, tools/h2_wino_vs_direct.py: 60x80x128 -> 128 0.435 Winograd | 0.352 direct; p2 256 -> 256
-        # 3.99 | 4.85).  A function of the layer only.
-        use_wino = False
-    if use_wino and precision == 3 and WINO_MAX_HW and H * W > WINO_MAX_HW and p.presplit and (-(-p.cols // 256) * 256 <= p.cols + p.cols // 4):
-        # (experiment knob, a function of the layer and the image size only: 3x3 layers on maps larger than A3D_WINO_MAX_HW pixels take
-        # the wide DIRECT kernel -- same time as Winograd alone on the p2 / p3 levels, a fifth of its HBM traffic)
-        use_wino = False
-        d.tune = 9
-    ws = None
+        d.w_scale = filter_scale(p)
+    if precision in (2, 3) and (DEFAULT_PRECISION == 3 or precision == 3) and not p.pixshuf:
+        d.y_amax = _y_amax(out)
     if use_wino:
-        if WINO_TUNE and d.tune == 0 and d.precision == 3:
-            d.tune = WINO_TUNE
         d.w_wino = p.w_wino.data_ptr()
-        if p.w_wino_cm is not None and d.precision == 0 and tune == 0:
+        if p.w_wino_cm is not None and precision == 0 and tune == 0:
             d.w_wino_cm = p.w_wino_cm.data_ptr()  # the library then takes the one-launch kernel where the layer qualifies
-        if d.precision == 3:  # the Winograd-domain filter as two fp16 planes, scaled by the power of two of ITS maximum
-            if getattr(p, "_u_scale", None) is None:
-                p._u_scale = _pow2_scale_host(float(p.w_wino.abs().max()))
-            d.w_scale = p._u_scale
-            if p.w_wino_h2 is None or p.w_wino_h2.device != p.w_wino.device:
-                rows, cols = p.w_wino.shape[1], p.w_wino.shape[2]
-                p.w_wino_h2 = torch.empty((16, cols // 32, 2, rows, 32), device=p.w_wino.device, dtype=torch.float16)
-                _lib.check(_lib.lib().a3d_split_f16x2_chunk(p.w_wino.data_ptr(), p.w_wino_h2.data_ptr(), 16, rows, cols, 32, p._u_scale, _stream()),
-                           "a3d_split_f16x2_chunk")
-                if not os.environ.get("A3D_NO_PUBLISH"):
-                    torch.cuda.current_stream().synchronize()
-            d.w_wino_x3 = p.w_wino_h2.data_ptr()
-        if d.precision == 2:
-            if p.w_wino_x3 is None or p.w_wino_x3.device != p.w_wino.device:  # once per layer
-                rows, cols = p.w_wino.shape[1], p.w_wino.shape[2]
-                p.w_wino_x3 = torch.empty((16, cols // 32, 3, rows, 32), device=p.w_wino.device, dtype=torch.bfloat16)
-                _lib.check(_lib.lib().a3d_split_bf16x3(p.w_wino.data_ptr(), p.w_wino_x3.data_ptr(), 16, rows, cols, _stream()), "a3d_split_bf16x3")
-                # the cache is read by later launches on ANY stream (the RPN head runs one packed layer on three streams for 1-2
-                # frame batches): it must be complete before it is published.  Once per packed layer.
-                if not os.environ.get("A3D_NO_PUBLISH"):
-                    torch.cuda.current_stream().synchronize()
-            d.w_wino_x3 = p.w_wino_x3.data_ptr()
-    if d.precision == 3 and not use_wino and p.presplit and p.Kpad % 16 == 0:
-        # every direct fp16x2 launch of a module-cached layer streams its filter pre-split by LDS-DMA (narrow and wide kernels alike)
-        if p.w_h2 is None or p.w_h2.device != p.w.device:  # the fp16x2 planes of the filter, scaled by w_scale (once per packed layer)
-            p.w_h2 = torch.empty((p.Kpad // 16, 2, p.w.shape[0], 16), device=p.w.device, dtype=torch.float16)
-            _lib.check(_lib.lib().a3d_split_f16x2_chunk(p.w.data_ptr(), p.w_h2.data_ptr(), 1, p.w.shape[0], p.Kpad, 16, d.w_scale, _stream()),
-                       "a3d_split_f16x2_chunk")
-            if not os.environ.get("A3D_NO_PUBLISH"):
-                torch.cuda.current_stream().synchronize()  # published to every stream, see w_wino_x3 below
-        d.w_x3 = p.w_h2.data_ptr()
-    if (d.precision == 2 and not use_wino and p.presplit and p.cols >= 192 and p.Kpad % 16 == 0 and (p.Kpad >= 4096 or tune == 9 or p.phase == 5)
+        if precision == 3:  # the Winograd-domain filter as two fp16 planes, scaled by the power of two of ITS maximum
+            d.w_scale = filter_scale(p, wino=True)
+            d.w_wino_x3 = weight_planes(p, "w_wino_h2")
+        elif precision == 2:
+            d.w_wino_x3 = weight_planes(p, "w_wino_x3")
+    elif precision == 3 and p.presplit and p.Kpad % 16 == 0:
+        d.w_x3 = weight_planes(p, "w_h2")  # every direct fp16x2 launch of a module-cached layer streams its filter pre-split by LDS-DMA
+    elif (precision == 2 and p.presplit and p.cols >= 192 and p.Kpad % 16 == 0 and (p.Kpad >= 4096 or tune == 9 or p.phase == 5)
             and not (p.stem or p.pixshuf)):
-        # wide layers: weight planes pre-split once per packed layer, streamed by LDS-DMA (csrc/conv_bf16x3_wide.hip)
-        if p.w_x3 is None or p.w_x3.device != p.w.device:
-            p.w_x3 = torch.empty((p.Kpad // 16, 3, p.w.shape[0], 16), device=p.w.device, dtype=torch.bfloat16)
-            _lib.check(_lib.lib().a3d_split_bf16x3_chunk(p.w.data_ptr(), p.w_x3.data_ptr(), 1, p.w.shape[0], p.Kpad, 16, _stream()), "a3d_split_bf16x3_chunk")
-            if not os.environ.get("A3D_NO_PUBLISH"):
-                torch.cuda.current_stream().synchronize()  # published to every stream, see w_wino_x3 above
-        d.w_x3 = p.w_x3.data_ptr()
+        d.w_x3 = weight_planes(p, "w_x3")  # wide layers: weight planes pre-split once per packed layer (csrc/conv_bf16x3_wide.hip)
+    ws = None
     fused_wino = False
     shared = None  # [input tensor, its transformed tiles V or None]: see share_wino_input
     nbytes = mbytes = 0
     if use_wino or splitk > 1:
         if use_wino and _WINO_SHARE is not None and x2 is None:
             shared = _WINO_SHARE.get(x.data_ptr())
-            if shared is not None and (shared[0].shape != x.shape or d.tune not in (0, 23, 24)):  # (23 | 24: other loops of the same GEMM on the same V)
+            if shared is not None and (shared[0].shape != x.shape or tune not in (0, 23, 24)):  # (23 | 24: other loops of the same GEMM on the same V)
                 shared = None
             # (the tiles' FORMAT belongs to the arithmetic: fp16x2 consumers read V pre-split into fp16 planes, the others fp32)
-            if shared is not None and shared[1] is not None and len(shared) > 2 and shared[2] != int(d.precision):
+            if shared is not None and shared[1] is not None and len(shared) > 2 and shared[2] != precision:
                 shared = None
         if shared is not None:
             d.w_wino_cm = None  # consumers of a shared input take the two-launch form so that V exists once for all of them
@@ -941,44 +949,44 @@ def _conv2d_launch(x: torch.Tensor, p: PackedConv, *, x2: Optional[torch.Tensor]
         elif nbytes:
             ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
             d.workspace = ws.data_ptr()
-        if use_wino and d.precision == 3 and WINO_PLANE_SPLIT:  # small problems: scratch for the plane-split form (a3d_conv_desc.wino_m; 0 bytes otherwise)
+        if use_wino and precision == 3 and WINO_PLANE_SPLIT:  # small problems: scratch for the plane-split form (a3d_conv_desc.wino_m; 0 bytes otherwise)
             mbytes = _lib.lib().a3d_wino_m_bytes(C.byref(d))
             if mbytes:
                 wino_m = torch.empty(mbytes // 4, device=x.device, dtype=torch.float32)
                 d.wino_m = wino_m.data_ptr()
+    have_v = False
     if shared is not None:
         have_v, shared[1] = shared[1] is not None, ws
         if len(shared) > 2:
-            shared[2] = int(d.precision)
+            shared[2] = precision
         else:
-            shared.append(int(d.precision))
-    # CONV_TIMING_ONLY (a set of variant labels): event pairs only around the launches whose label -- remembered from the last fully
-    # instrumented pass over the same layer and shape -- is in the set; every other launch goes out as if nothing were measured
-    # (700 event pairs per 64-frame step cost 0.8 ms of its 44).
-    timing = CONV_TIMING is not None
-    tkey = None
-    if timing:
-        tkey = (id(p), B, H, W, bool(ups), int(splitk), int(d.precision), int(d.tune), res is not None, x2 is not None, shared is not None)
-        if CONV_TIMING_ONLY is not None:
-            known = _TIMED_VARIANTS.get(tkey)
-            timing = known is None or bool(known & CONV_TIMING_ONLY)
-    if shared is not None and not timing:
+            shared.append(precision)
+
+    def rec(label=None):  # CONV_TIMING's record; the algorithmic FLOPs of a phase launch = its share (1/4) of the 3x3 conv over the upsampled tensor
+        k_real = 147 if p.stem else p.KH * p.KW * p.Cin
+        shape = f"{B}x{H}x{W}x{Cin + Cin2}->{p.cols} k{p.KH} s{p.stride}{' ups' if ups else ''}{' sk%d' % splitk if splitk > 1 else ''}"
+        if label is not None:
+            return label, 0.0, shape, 0.0, "none", None
+        fl = 2.0 * B * Ho * Wo * p.cols * (9 * p.Cin if p.phase else k_real)
+        if use_wino:  # (16 multiply-adds per 2x2 output tile and channel pair instead of 36)
+            ex = 2.0 * B * ((Ho + 1) // 2) * ((Wo + 1) // 2) * 16 * p.cols * p.Cin
+        else:  # (fused phases: 4 of the 9 taps per column)
+            ex = 2.0 * B * Ho * Wo * p.cols * (4 * p.Cin if p.phase == 5 else k_real)
+        return None, fl, shape, ex, _PIPE[precision], (id(p), B, H, W, bool(ups), int(splitk), precision, tune, res is not None, x2 is not None, shared is not None)
+
+    L = _lib.lib()
+    if use_wino and not fused_wino and (shared is not None or CONV_TIMING is not None):
+        # the two launches of the Winograd form as separate calls: a shared input's V is transformed once; measurement times each kernel
         if not have_v:
-            _lib.check(_lib.lib().a3d_wino_input_transform(C.byref(d), _stream()), "a3d_wino_input_transform")
-        _lib.check(_lib.lib().a3d_wino_gemm(C.byref(d), _stream()), "a3d_wino_gemm")
+            _launch(L.a3d_wino_input_transform, C.byref(d), precision=precision, rec=lambda: rec("wino_input_kernel"))
+        _launch(L.a3d_wino_gemm, C.byref(d), precision=precision, rec=rec)
         return out
-    if timing:
-        n_before = len(CONV_TIMING)
-        try:
-            return _conv2d_timed(d, p, out, shared, have_v if shared is not None else False, use_wino, fused_wino, B, H, W, Ho, Wo, Cin, Cin2, ups, splitk)
-        finally:
-            _TIMED_VARIANTS[tkey] = frozenset(t[0] for t in CONV_TIMING[n_before:])
-    _lib.check(_lib.lib().a3d_conv2d_nhwc_f32(C.byref(d), _stream()), "a3d_conv2d_nhwc_f32")
-    if plan_key is not None and shared is None:
+    _launch(L.a3d_conv2d_nhwc_f32, C.byref(d), precision=precision, rec=rec)
+    if plan_key is not None:
         if p.__dict__.get("_plans") is None or len(p._plans) > 64:
             p._plans = {}
         p._plans[plan_key] = (bytes(d), tuple(out.shape), bool(d.in_amax), bool(d.y_amax), nbytes // 4 if ws is not None else 0,
-                              mbytes // 4 if d.wino_m else 0, int(precision))
+                              mbytes // 4 if d.wino_m else 0, precision)
     return out
 
 
@@ -1014,92 +1022,25 @@ def conv2d_b2b(x: torch.Tensor, p1: PackedConv, res: torch.Tensor, p2: PackedCon
     _req(res)
     y = torch.empty((B, H, W, p1.cols), device=x.device, dtype=torch.float32)
     z = torch.empty((B, H, W, p2.cols), device=x.device, dtype=torch.float32)
-    d1, d2 = _lib.ConvDesc(), _lib.ConvDesc()
-    for d, p, xi, yo in ((d1, p1, x, y), (d2, p2, y, z)):
-        d.x, d.w, d.scale, d.shift, d.y = _p(xi), _p(p.w), _p(p.scale), _p(p.shift), _p(yo)
-        d.B, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout = B, H, W, p.Cin, H, W, p.cols
-        d.KH, d.KW, d.stride, d.pad, d.Kpad, d.act, d.splitk = 1, 1, 1, 0, p.Kpad, p.act, 1
-        ya = yo._a3d_amax = amax_slot(B, x.device)
-        d.y_amax = ya.data_ptr()
-    d1.res = res.data_ptr()
+    d1, d2 = _conv_desc(p1, B, H, W, Cin, 0, H, W), _conv_desc(p2, B, H, W, p2.Cin, 0, H, W)
+    d1.x, d1.res, d1.y, d1.y_amax = x.data_ptr(), res.data_ptr(), y.data_ptr(), _y_amax(y)
+    d2.x, d2.y, d2.y_amax = y.data_ptr(), z.data_ptr(), _y_amax(z)
     d1.precision, d2.precision = 3, 2
     d1.in_amax = amax_of(x).data_ptr()
-    if getattr(p1, "_w_scale", None) is None:
-        p1._w_scale = _pow2_scale_host(float(p1.w.abs().max()))
-    d1.w_scale = p1._w_scale
-    fresh = False
-    if p1.w_h2 is None or p1.w_h2.device != p1.w.device:  # (as _conv2d_launch: the fp16x2 planes of the filter, once per packed layer)
-        p1.w_h2 = torch.empty((p1.Kpad // 16, 2, p1.w.shape[0], 16), device=p1.w.device, dtype=torch.float16)
-        _lib.check(_lib.lib().a3d_split_f16x2_chunk(p1.w.data_ptr(), p1.w_h2.data_ptr(), 1, p1.w.shape[0], p1.Kpad, 16, d1.w_scale, _stream()), "a3d_split_f16x2_chunk")
-        fresh = True
-    if p2.w_x3 is None or p2.w_x3.device != p2.w.device:  # the second filter's exact bf16 planes, once per packed layer
-        p2.w_x3 = torch.empty((p2.Kpad // 16, 3, p2.w.shape[0], 16), device=p2.w.device, dtype=torch.bfloat16)
-        _lib.check(_lib.lib().a3d_split_bf16x3_chunk(p2.w.data_ptr(), p2.w_x3.data_ptr(), 1, p2.w.shape[0], p2.Kpad, 16, _stream()), "a3d_split_bf16x3_chunk")
-        fresh = True
-    if fresh and not os.environ.get("A3D_NO_PUBLISH"):
-        torch.cuda.current_stream().synchronize()  # (published to every stream, as the other per-layer caches)
-    d1.w_x3, d2.w_x3 = p1.w_h2.data_ptr(), p2.w_x3.data_ptr()
-    global _LAST_PRECISION
-    _LAST_PRECISION = 3
-    timing = CONV_TIMING is not None and (CONV_TIMING_ONLY is None or any(v.startswith("conv_h2xs_b2b") for v in CONV_TIMING_ONLY))
-    if timing:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = _lib.lib().a3d_conv_b2b(C.byref(d1), C.byref(d2), _stream())
-    if rc == -3:  # A3D_ERR_UNSUPPORTED: not a pair of this form after all
-        return None
-    _lib.check(rc, "a3d_conv_b2b")
-    if timing:
-        e1.record()
-        fl = 2.0 * M * (p1.cols * Cin + p2.cols * p2.Cin)
+    d1.w_scale = filter_scale(p1)
+    d1.w_x3, d2.w_x3 = weight_planes(p1, "w_h2"), weight_planes(p2, "w_x3")  # (the second filter's exact bf16 planes)
+
+    def rec():
         # (executed matrix FLOPs: 3 fp16 products per multiply-add of the first layer, 6 bf16 ones of the second -- booked at the fp16x2
         # weight of 3 with the second layer counted twice, so that the roofline object's issued-FLOP sum stays right)
-        ex = 2.0 * M * (p1.cols * Cin + 2 * p2.cols * p2.Cin)
-        CONV_TIMING.append((last_conv_variant(), fl, e0, e1, f"{B}x{H}x{W}x{Cin}->{p1.cols}->{p2.cols} k1 b2b", ex, "f16x3", _stream()))
+        fl, ex = 2.0 * M * (p1.cols * Cin + p2.cols * p2.Cin), 2.0 * M * (p1.cols * Cin + 2 * p2.cols * p2.Cin)
+        return None, fl, f"{B}x{H}x{W}x{Cin}->{p1.cols}->{p2.cols} k1 b2b", ex, "f16x3", (id(p1), id(p2), B, H, W)
+
+    if not _launch(_lib.lib().a3d_conv_b2b, C.byref(d1), C.byref(d2), precision=3, rec=rec, unsupported=True):
+        return None  # (not a pair of this form after all)
     return y, z
 
 
-CONV_TIMING_ONLY: Optional[frozenset] = None
-_TIMED_VARIANTS: dict = {}
-
-
-def _conv2d_timed(d, p, out, shared, have_v, use_wino, fused_wino, B, H, W, Ho, Wo, Cin, Cin2, ups, splitk):
-    """The launch of _conv2d_launch with HIP events around each kernel (CONV_TIMING)."""
-    k_real = 147 if p.stem else p.KH * p.KW * p.Cin
-    shape = f"{B}x{H}x{W}x{Cin + Cin2}->{p.cols} k{p.KH} s{p.stride}{' ups' if ups else ''}{' sk%d' % splitk if splitk > 1 else ''}"
-    ev = lambda: torch.cuda.Event(enable_timing=True)
-    tiles = B * ((Ho + 1) // 2) * ((Wo + 1) // 2)
-    if fused_wino:
-        e0, e1 = ev(), ev()
-        e0.record()
-        _lib.check(_lib.lib().a3d_conv2d_nhwc_f32(C.byref(d), _stream()), "a3d_conv2d_nhwc_f32")
-        e1.record()
-        CONV_TIMING.append((last_conv_variant(), 2.0 * B * Ho * Wo * p.cols * k_real, e0, e1, shape, 2.0 * tiles * 16 * p.cols * p.Cin, "f32", _stream()))
-        return out
-    if use_wino:  # the two launches of the Winograd form are timed separately (they are separate kernels)
-        e0, e1, e2 = ev(), ev(), ev()
-        e0.record()
-        if shared is None or not have_v:
-            _lib.check(_lib.lib().a3d_wino_input_transform(C.byref(d), _stream()), "a3d_wino_input_transform")
-        e1.record()
-        _lib.check(_lib.lib().a3d_wino_gemm(C.byref(d), _stream()), "a3d_wino_gemm")
-        e2.record()
-        CONV_TIMING.append(("wino_input_kernel", 0.0, e0, e1, shape, 0.0, "none", _stream()))
-        CONV_TIMING.append((last_conv_variant(), 2.0 * B * Ho * Wo * p.cols * k_real, e1, e2, shape, 2.0 * tiles * 16 * p.cols * p.Cin,
-                            {2: "bf16x6", 3: "f16x3"}.get(int(d.precision), "f32"), _stream()))
-        return out
-    e0, e1 = ev(), ev()
-    e0.record()
-    _lib.check(_lib.lib().a3d_conv2d_nhwc_f32(C.byref(d), _stream()), "a3d_conv2d_nhwc_f32")
-    e1.record()
-    # algorithmic FLOPs of a phase launch = its share (1/4) of the 3x3 conv over the upsampled tensor
-    executed = 2.0 * B * Ho * Wo * p.cols * (4 * p.Cin if p.phase == 5 else k_real)  # (fused phases: 4 of the 9 taps per column)
-    fl = 2.0 * B * Ho * Wo * p.cols * (9 * p.Cin) if p.phase else executed
-    CONV_TIMING.append((last_conv_variant(), fl, e0, e1, shape, executed, {0: "f32", 1: "bf16", 2: "bf16x6", 3: "f16x3"}[int(d.precision)], _stream()))
-    return out
-
-
-WINO_MAX_HW = int(os.environ.get("A3D_WINO_MAX_HW", "0"))
 WINO_TUNE = int(os.environ.get("A3D_WINO_TUNE", "0"))  # measurement knob: 23 | 24 = every fp16x2 Winograd GEMM in its lockstep | 64-tile form (the same bits)
 UPS_FUSED = os.environ.get("A3D_UPS_FUSED", "1") != "0"  # (False: always the four-launch form; same bits)
 
@@ -1163,13 +1104,9 @@ def conv2d_ups_to1(x: torch.Tensor, phases: Sequence[PackedConv], w9: torch.Tens
     # allocated.  A batch past the 32-bit offsets runs as blocks of images through the SAME two kernels (per-image arithmetic: the
     # bits of a frame do not depend on the block it travels in), never through another algorithm.
     per_image = max(9 * 4 * H * W * 4, H * W * C * 4, 0 if x2 is None else x2.shape[1] * x2.shape[2] * x2.shape[3] * 4)
-    nb = max(1, min(B, _ADDR_LIMIT // per_image))
     y = torch.empty((B, 2 * H, 2 * W), device=x.device, dtype=torch.float32)
     w9 = w9.reshape(9, 64)
-    for b0 in range(0, B, nb):
-        b1 = min(B, b0 + nb)
-        cut = lambda t: t if (t is None or nb >= B) else keep_amax(t[b0:b1], _amax_rows(t, b0, b1))
-        xb, x2b = cut(x), cut(x2)
+    for b0, b1, (xb, x2b) in _image_blocks(B, max(1, _ADDR_LIMIT // per_image), x, x2):
         g = torch.empty((b1 - b0, 9, 2 * H, 2 * W), device=x.device, dtype=torch.float32)
         conv2d(xb, pf, x2=x2b, out=g, precision=3, dot=(w9, g))
         _lib.check(_lib.lib().a3d_tapsum9(g.data_ptr(), float(bias), y[b0:b1].data_ptr(), b1 - b0, 2 * H, 2 * W, _stream()), "a3d_tapsum9")
@@ -1360,38 +1297,19 @@ def stem_pool(x: torch.Tensor, p: "PackedConv") -> Optional[torch.Tensor]:
     Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
     Hp, Wp = (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1
     out = torch.empty((B, Hp, Wp, 64), device=x.device, dtype=torch.float32)
-    d = _lib.ConvDesc()
-    d.x, d.w, d.scale, d.shift, d.y = _p(x), _p(p.w), _p(p.scale), _p(p.shift), _p(out)
-    d.B, d.H, d.W, d.Cin, d.Cin2 = B, H, W, 4, 0
-    d.Ho, d.Wo, d.Cout = Ho, Wo, 64
-    d.KH, d.KW, d.stride, d.pad = 7, 7, 2, 3
-    d.Kpad, d.act, d.stem, d.splitk, d.precision = p.Kpad, p.act, 1, 1, 3
+    d = _conv_desc(p, B, H, W, 4, 0, Ho, Wo)
+    d.KH, d.KW, d.stride, d.pad, d.Cout = 7, 7, 2, 3, 64  # (what the fused kernel computes)
+    d.x, d.y, d.precision = x.data_ptr(), out.data_ptr(), 3
     d.tune = int(os.environ.get("A3D_STEM_ABL", "0"))  # (developer builds with -DA3D_ABLATIONS only: timing-only variants)
     d.in_amax = amax_of(x).data_ptr()
-    if getattr(p, "_w_scale", None) is None:
-        p._w_scale = _pow2_scale_host(float(p.w.abs().max()))
-    d.w_scale = p._w_scale
-    if p.w_h2 is None or p.w_h2.device != p.w.device:  # (the filter's fp16 planes: the cache ops.conv2d fills for every direct fp16x2 layer)
-        p.w_h2 = torch.empty((p.Kpad // 16, 2, p.w.shape[0], 16), device=p.w.device, dtype=torch.float16)
-        _lib.check(_lib.lib().a3d_split_f16x2_chunk(p.w.data_ptr(), p.w_h2.data_ptr(), 1, p.w.shape[0], p.Kpad, 16, d.w_scale, _stream()),
-                   "a3d_split_f16x2_chunk")
-        if not os.environ.get("A3D_NO_PUBLISH"):
-            torch.cuda.current_stream().synchronize()
-    d.w_x3 = p.w_h2.data_ptr()
-    if not os.environ.get("A3D_NO_YAMAX"):
-        out._a3d_amax = amax_slot(B, out.device)
-        d.y_amax = out._a3d_amax.data_ptr()
-    global _LAST_PRECISION
-    _LAST_PRECISION = 3
-    if CONV_TIMING is not None and CONV_TIMING_ONLY is None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _lib.check(_lib.lib().a3d_stem_conv_pool(C.byref(d), _stream()), "a3d_stem_conv_pool")
-        e1.record()
+    d.w_scale, d.w_x3 = filter_scale(p), weight_planes(p, "w_h2")  # (the filter's fp16 planes: the cache ops.conv2d fills for every direct fp16x2 layer)
+    d.y_amax = _y_amax(out)
+
+    def rec():
         fl = 2.0 * B * Ho * Wo * 64 * 147
-        CONV_TIMING.append(("stem_pool_kernel", fl, e0, e1, f"{B}x{H}x{W}x4->64 k7 s2 + pool", fl, "f16x3", _stream()))
-        return out
-    _lib.check(_lib.lib().a3d_stem_conv_pool(C.byref(d), _stream()), "a3d_stem_conv_pool")
+        return "stem_pool_kernel", fl, f"{B}x{H}x{W}x4->64 k7 s2 + pool", fl, "f16x3", None
+
+    _launch(_lib.lib().a3d_stem_conv_pool, C.byref(d), precision=3, rec=rec)
     return out
 
 

@@ -122,19 +122,14 @@ def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, *, KH: int, 
         defer.items.append(keep)
     from . import ops as _ops
 
-    if _ops.CONV_TIMING is not None:  # tools/train_bench.py's roofline leg: HIP events around the launch, same record as ops.conv2d's
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _lib.check(_lib.lib().a3d_conv_wgrad_nhwc_f32(C.byref(d), _stream()), "a3d_conv_wgrad_nhwc_f32")
-        e1.record()
+    def rec():  # tools/train_bench.py's roofline leg: the same record as ops.conv2d's
         fl = 2.0 * B * Ho * Wo * Cout * KH * KW * Cin  # the pixel-reduction GEMM dY^T . X per tap = the layer's forward FLOPs
         label = {0: "conv_wgrad_kernel", 1: f"conv_wgrad_bf16_kernel<false, {d.io_bf16}>", 2: "conv_wgrad_bf16_kernel<true, 0>"}[int(precision)]
         if form > 0:
             label = f"conv_wgrad_tr_kernel<{form}, {d.io_bf16}>"
-        _ops.CONV_TIMING.append((label, fl, e0, e1, f"{B}x{H}x{W}x{Cin}->{Cout} k{KH} s{stride} wgrad sk{d.splitk}", fl,
-                                 {0: "f32", 1: "bf16", 2: "bf16x6"}[int(precision)], _stream()))
-        return dw
-    _lib.check(_lib.lib().a3d_conv_wgrad_nhwc_f32(C.byref(d), _stream()), "a3d_conv_wgrad_nhwc_f32")
+        return label, fl, f"{B}x{H}x{W}x{Cin}->{Cout} k{KH} s{stride} wgrad sk{d.splitk}", fl, {0: "f32", 1: "bf16", 2: "bf16x6"}[int(precision)], None
+
+    _ops._launch(_lib.lib().a3d_conv_wgrad_nhwc_f32, C.byref(d), rec=rec)
     return dw
 
 
