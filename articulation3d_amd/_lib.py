@@ -122,6 +122,16 @@ class WgradDesc(C.Structure):
         ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("Ho", C.c_int), ("Wo", C.c_int), ("Cout", C.c_int),
         ("KH", C.c_int), ("KW", C.c_int), ("stride", C.c_int), ("pad", C.c_int),
         ("splitk", C.c_int), ("accumulate", C.c_int), ("precision", C.c_int), ("io_bf16", C.c_int), ("defer_reduce", C.c_int),
+        ("p_dev", fptr),
+    ]
+
+
+class AxisLossDesc(C.Structure):
+    _fields_ = [
+        ("raw_rot", fptr), ("raw_tran", fptr), ("live", fptr), ("row_img", fptr), ("row_gt", fptr), ("gt_rot_axis", fptr),
+        ("gt_tran_axis", fptr), ("loss", fptr), ("d_rot", fptr), ("d_tran", fptr),
+        ("rows", C.c_int), ("rot_pitch", C.c_int), ("tran_pitch", C.c_int), ("B", C.c_int), ("max_gt", C.c_int),
+        ("beta", C.c_float), ("loss_weight", C.c_float),
     ]
 
 
@@ -249,6 +259,8 @@ SIGNATURES = {
     "a3d_colsum_workspace_bytes": (C.c_size_t, [C.c_int]),
     "a3d_colsum": (C.c_int, [fptr, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr]),
     "a3d_colsum_bf16": (C.c_int, [fptr, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr]),
+    "a3d_colsum_rows": (C.c_int, [fptr, C.c_int, fptr, fptr, C.c_int, fptr, C.c_int, C.c_int, fptr]),
+    "a3d_axis_loss": (C.c_int, [C.POINTER(AxisLossDesc), fptr]),
     "a3d_roi_align_fpn_backward": (C.c_int, [C.POINTER(RoiAlignBwdDesc), fptr]),
     "a3d_roi_align_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(RoiAlignBwdDesc)]),
     "a3d_roi_align_fpn_backward_gather": (C.c_int, [C.POINTER(RoiAlignBwdDesc), fptr, fptr]),
@@ -270,7 +282,8 @@ SIGNATURES = {
 }
 
 STRUCT_IDS = {0: ConvDesc, 1: RpnDesc, 2: BoxDetDesc, 3: RoiAlignDesc, 4: PasteDesc, 5: PackDesc, 6: WgradDesc,
-              7: RoiAlignBwdDesc, 8: MatchDesc, 9: RpnLossDesc, 10: BoxLossDesc, 11: RoiSampleDesc, 12: SweepDesc, 13: TransposeItem}
+              7: RoiAlignBwdDesc, 8: MatchDesc, 9: RpnLossDesc, 10: BoxLossDesc, 11: RoiSampleDesc, 12: SweepDesc, 13: TransposeItem,
+              14: AxisLossDesc}
 
 _lib = None
 

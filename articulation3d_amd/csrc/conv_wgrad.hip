@@ -17,10 +17,21 @@
 
 namespace {
 constexpr int WG_BK = 16;    // pixels per chunk
+
+// a3d_wgrad_desc.p_dev: the live pixels [0, P) and the slice length that divides THEM (the host's formula on the live count: the full
+// count gives the host's chunk, so the bits of the NULL form)
+__device__ __forceinline__ void wg_live(const a3d_wgrad_desc &d, int &P, int &chunk) {
+    if (!d.p_dev) return;
+    const int n = __builtin_amdgcn_readfirstlane(*d.p_dev);
+    P = n < 0 ? 0 : (n < P ? n : P);
+    chunk = (P + d.splitk - 1) / d.splitk;
+    chunk = (chunk + 31) / 32 * 32;
+}
 constexpr int WG_LD = 160;   // LDS row pitch in floats
 
-__global__ __launch_bounds__(256) void conv_wgrad_kernel(const a3d_wgrad_desc d, const int P, const int mtiles, const int ntiles,
-                                                          const int chunk) {
+__global__ __launch_bounds__(256) void conv_wgrad_kernel(const a3d_wgrad_desc d, int P, const int mtiles, const int ntiles,
+                                                          int chunk) {
+    wg_live(d, P, chunk);
     __shared__ __attribute__((aligned(16))) float lds[2][2][WG_BK * WG_LD];  // [buffer][A|B][k][channel]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -168,7 +179,7 @@ __device__ __forceinline__ void wg_split3(const wg_f32x8 v, wg_bf16x8 &h, wg_bf1
 // the staging registers it uses).
 template <bool X3, int IO = 0>
 __global__ __launch_bounds__(256, X3 ? 2 : 3) void conv_wgrad_bf16_kernel(const a3d_wgrad_desc d, const int P, const int mtiles, const int ntiles,
-                                                                         const int chunk) {
+                                                                         int chunk) {
     constexpr int BKP = X3 ? 16 : 32, LKB = BKP + 8, NPL = X3 ? 3 : 1, G = BKP / 16, S = BKP / 16;
     constexpr int PL = 128 * LKB;  // one operand plane: [channel][pixel]
     __shared__ __attribute__((aligned(16))) __bf16 lds[2][2][NPL * PL];  // [buffer][A|B][plane][channel][pixel]
@@ -181,7 +192,9 @@ __global__ __launch_bounds__(256, X3 ? 2 : 3) void conv_wgrad_bf16_kernel(const 
     const int tap = t / mtiles;
     const int kh = tap / d.KW, kw = tap - kh * d.KW;
     const int co0 = mt * 128, ci0 = nt * 128;
-    const int p_begin = blockIdx.y * chunk, p_end = min(P, p_begin + chunk);
+    int Pl = P;  // (P itself sizes the buffer descriptors)
+    wg_live(d, Pl, chunk);
+    const int p_begin = blockIdx.y * chunk, p_end = min(Pl, p_begin + chunk);
     const int ch = tid & 127, kg = tid >> 7;  // channel inside the tile; pixel groups kg*G .. kg*G+G-1 (8 pixels each)
     const bool a_ok = co0 + ch < d.Cout, b_ok = ci0 + ch < d.Cin;
     const int HoWo = d.Ho * d.Wo;

@@ -40,7 +40,7 @@ constexpr int tr_lds_bytes(int NT, int TA, int TB) { return 2 * tr_stage_bytes(N
 // XB / YB: x / dy stored as bf16.
 template <int NT, int MB, int NB, int WM, int WN, bool XB, bool YB>
 __global__ __launch_bounds__(64 * WM * WN, 1) void conv_wgrad_tr_kernel(const a3d_wgrad_desc d, const int Pp, const int Wp, const float invWp, const float invHo,
-                                                                        const int mtiles, const int ntiles, const int chunk) {
+                                                                        const int mtiles, const int ntiles, int chunk) {
     constexpr int NTH = 64 * WM * WN;
     constexpr int TA = 32 * MB * WM, TB = 32 * NB * WN;
     constexpr int RA = 2 * TA, RB = 2 * TB;                            // bytes of an LDS row
@@ -60,7 +60,17 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_wgrad_tr_kernel(const a3
     const int mt = t % mtiles;
     const int kh = t / mtiles;  // filter row (NT == 3) or 0
     const int co0 = mt * TA, ci0 = nt * TB;
-    const int p_begin = blockIdx.y * chunk, p_end = min(Pp, p_begin + chunk);
+    // a3d_wgrad_desc.p_dev: live output pixels (whole images) -> the live reduction [0, Ppl) in this form's numbering, sliced as the host
+    // slices the full one (the full count gives the host's chunk: the NULL bits).  x rows past Ppl are never read, not even as a shifted tap.
+    int Ppl = Pp;
+    if (d.p_dev) {
+        const int n = __builtin_amdgcn_readfirstlane(*d.p_dev), full = d.B * d.Ho * d.Wo;
+        const int live = n < 0 ? 0 : (n < full ? n : full);
+        Ppl = NT == 3 ? (live / (d.Ho * d.Wo)) * d.Ho * Wp : live;
+        chunk = (Ppl + d.splitk - 1) / d.splitk;
+        chunk = (chunk + TR_CH - 1) / TR_CH * TR_CH;
+    }
+    const int p_begin = blockIdx.y * chunk, p_end = min(Ppl, p_begin + chunk);
     const int nchunks = (p_end - p_begin + TR_CH - 1) / TR_CH;
 
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(d.dy), 0, (int)(((size_t)d.B * d.Ho * d.Wo * d.Cout * 4) >> (YB ? 1 : 0)), 0x00020000);
@@ -95,7 +105,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_wgrad_tr_kernel(const a3
                 const int kap = k0 - 1 + row;
                 const int q = (int)(((float)kap + 0.5f) * invWp), j = kap - q * Wp;
                 const int b = (int)(((float)q + 0.5f) * invHo), ih = q - b * d.Ho + kh - 1;
-                if (row < ROWS_B && kap >= 0 && kap < Pp && (unsigned)j < (unsigned)d.W && (unsigned)ih < (unsigned)d.H && cvb) off = (((b * d.H + ih) * d.W + j) * d.Cin + chb) * (XB ? 2 : 4);
+                if (row < ROWS_B && kap >= 0 && kap < Ppl && (unsigned)j < (unsigned)d.W && (unsigned)ih < (unsigned)d.H && cvb) off = (((b * d.H + ih) * d.W + j) * d.Cin + chb) * (XB ? 2 : 4);
             } else {
                 const int kap = k0 + row;
                 if (kap < p_end && cvb) off = (kap * d.Cin + chb) * (XB ? 2 : 4);

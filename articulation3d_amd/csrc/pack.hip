@@ -187,6 +187,7 @@ extern "C" size_t a3d_struct_size(int id) {
         case 11: return sizeof(a3d_roi_sample_desc);
         case 12: return sizeof(a3d_sweep_desc);
         case 13: return sizeof(a3d_transpose_item);
+        case 14: return sizeof(a3d_axis_loss_desc);
         default: return 0;
     }
 }

@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float *__restri
 // 315 MB gradients at 0.7 TB/s, 2.5 ms of a 31 ms step at 16 images; fixed summation order: rows r, r+16, .. per accumulator, then
 // ((a0 + a1) + (a2 + a3)), the 4 row phases as above)
 template <bool BF>  // BF: dy is stored as bf16 (widening is exact: the same sums as on the widened values)
-__global__ __launch_bounds__(256) void colsum_partial4_kernel(const void *__restrict__ dyv, float *__restrict__ ws, int M, int C, int rows_per) {
+__device__ __forceinline__ void colsum_partial4(const void *__restrict__ dyv, float *__restrict__ ws, int M, int C, int rows_per) {
     const int c = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
     const int sub = threadIdx.x >> 6;
     const int r0 = blockIdx.y * rows_per, r1 = min(M, r0 + rows_per);
@@ -255,6 +255,20 @@ __global__ __launch_bounds__(256) void colsum_partial4_kernel(const void *__rest
     if (sub == 0 && c < C)
         *reinterpret_cast<f32x4 *>(ws + (size_t)blockIdx.y * C + c) = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
+template <bool BF>
+__global__ __launch_bounds__(256) void colsum_partial4_kernel(const void *__restrict__ dyv, float *__restrict__ ws, int M, int C, int rows_per) {
+    colsum_partial4<BF>(dyv, ws, M, C, rows_per);
+}
+// a3d_colsum_rows: the live rows [0, *m_dev) only, dealt to `want` slices as a3d_colsum deals all M rows (an empty slice stores its zeros:
+// the final kernel reads every slice of the grid).  The full count gives a3d_colsum's slicing, so its bits.
+template <bool BF>
+__global__ __launch_bounds__(256) void colsum_rows_partial4_kernel(const void *__restrict__ dyv, float *__restrict__ ws, int M, const int *__restrict__ m_dev,
+                                                                   int C, int want) {
+    const int n = __builtin_amdgcn_readfirstlane(*m_dev);
+    const int Ml = n < 0 ? 0 : (n < M ? n : M);
+    const int a = (Ml + want - 1) / want, b = (Ml + (int)gridDim.y - 1) / (int)gridDim.y;  // (b: every live row lands in a slice of the grid)
+    colsum_partial4<BF>(dyv, ws, Ml, C, a > b ? a : b);
+}
 
 #define A3D_COLSUM_SLICES 256
 extern "C" size_t a3d_colsum_workspace_bytes(int C) { return (size_t)A3D_COLSUM_SLICES * C * sizeof(float); }
@@ -281,6 +295,22 @@ extern "C" int a3d_colsum(const float *dy, float *out, float *workspace, int M, 
 }
 extern "C" int a3d_colsum_bf16(const void *dy, float *out, float *workspace, int M, int C, int accumulate, void *stream) {
     return colsum_launch(dy, true, out, workspace, M, C, accumulate, stream);
+}
+extern "C" int a3d_colsum_rows(const void *dy, int bf16, float *out, float *workspace, int M, const int *m_dev, int C, int accumulate, void *stream) {
+    if (!dy || !out || !workspace || !m_dev || M <= 0 || C <= 0 || (C & 3)) return A3D_ERR_ARG;
+    if (reinterpret_cast<size_t>(dy) & (bf16 ? 7 : 15)) return A3D_ERR_ARG;
+    // the slices of the full buffer (a3d_colsum's grid); the rows per slice follow from the live count on the device
+    int want = M / 512;
+    want = want < 32 ? 32 : (want > A3D_COLSUM_SLICES ? A3D_COLSUM_SLICES : want);
+    const int rows_per = (M + want - 1) / want;
+    const int slices = (M + rows_per - 1) / rows_per;
+    a3d_begin();
+    if (bf16)
+        hipLaunchKernelGGL(colsum_rows_partial4_kernel<true>, dim3((C + 255) / 256, slices), dim3(256), 0, (hipStream_t)stream, dy, workspace, M, m_dev, C, want);
+    else
+        hipLaunchKernelGGL(colsum_rows_partial4_kernel<false>, dim3((C + 255) / 256, slices), dim3(256), 0, (hipStream_t)stream, dy, workspace, M, m_dev, C, want);
+    hipLaunchKernelGGL(colsum_final_kernel, dim3((C + 63) / 64), dim3(256), 0, (hipStream_t)stream, workspace, out, C, slices, accumulate);
+    return a3d_check_launch();
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -263,13 +263,36 @@ class PlaneRCNN(nn.Module):
         return self.training_forward(batched_inputs)
 
     # ------------------------------------------------------------------ training branch (planercnn.py:83-123)
+    STAGE2_FREEZE = ("backbone", "proposal_generator", "roi_heads.box_head", "roi_heads.box_predictor")
+
+    def training_stage(self) -> int:
+        """Which of the reference's training stages this model's configuration is: 1 (config/step1_bbox.yaml: box branch only) or
+        2 (config/step2_axis.yaml: AXIS_ON, MASK / PLANE / DEPTH off, FREEZE covering the four detector modules).  Anything else
+        (step3_plane.yaml's mask / plane / depth losses among it) raises NotImplementedError."""
+        rh = self.roi_heads
+        others = self.depth_head_on or getattr(rh, "mask_on", False) or getattr(rh, "plane_on", False)
+        axis = getattr(rh, "axis_on", False)
+        if not others and not axis:
+            return 1
+        if not others and axis and set(self.STAGE2_FREEZE) <= set(self._freeze):
+            return 2
+        raise NotImplementedError("training is implemented for config/step1_bbox.yaml (MASK_ON / PLANE_ON / AXIS_ON / DEPTH_ON false) and "
+                                  "config/step2_axis.yaml (AXIS_ON true, MASK_ON / PLANE_ON / DEPTH_ON false, FREEZE: " + str(list(self.STAGE2_FREEZE)) +
+                                  "); the mask, plane and depth losses of step3_plane.yaml are out of scope")
+
     def trainer(self, solver=None, precision: str = "bf16x3"):
         """The hand-written training step behind the reference's training-mode call: created on first use (it copies every
-        trainable parameter into its flat buffer).  `articulation3d_amd.engine.build_optimizer` returns the optimiser bound to it."""
+        trainable parameter into its flat buffer).  `articulation3d_amd.engine.build_optimizer` returns the optimiser bound to it.
+        Stage 1: DetectorTrainer; stage 2: training_axis.AxisTrainer (see training_stage)."""
         if getattr(self, "_trainer", None) is None:
-            from ..training import DetectorTrainer
+            if self.training_stage() == 2:
+                from ..training_axis import AxisTrainer
 
-            self._trainer = DetectorTrainer(self, solver, precision=precision)
+                self._trainer = AxisTrainer(self, solver, precision=precision)
+            else:
+                from ..training import DetectorTrainer
+
+                self._trainer = DetectorTrainer(self, solver, precision=precision)
         return self._trainer
 
     def training_forward(self, batched_inputs):
@@ -280,10 +303,7 @@ class PlaneRCNN(nn.Module):
         scalars accept `.backward()` so the reference's loop body stays as it is, and `engine.build_optimizer(cfg, model).step()`
         applies the fused all-reduce + SGD launch.  Only the step1_bbox configuration (BASELINE configs[4]: box branch; mask /
         plane / axis / depth heads off) has a training path."""
-        rh = self.roi_heads
-        if self.depth_head_on or getattr(rh, "mask_on", False) or getattr(rh, "plane_on", False) or getattr(rh, "axis_on", False):
-            raise NotImplementedError("training is implemented for config/step1_bbox.yaml (MASK_ON / PLANE_ON / AXIS_ON / DEPTH_ON false): "
-                                      "the mask, plane, axis and depth losses of the later training stages are outside SURVEY.md 8f-1")
+        stage = self.training_stage()
         assert "instances" in batched_inputs[0], "training needs ground-truth instances (planercnn.py:84-85)"
         imgs = [x["image"] for x in batched_inputs]
         assert all(tuple(t.shape) == tuple(imgs[0].shape) for t in imgs), "one image size per batch (the reference trains on 480x640 frames)"
@@ -293,7 +313,12 @@ class PlaneRCNN(nn.Module):
         gt_boxes = [x["instances"].gt_boxes.tensor.float() for x in batched_inputs]
         gt_classes = [x["instances"].gt_classes.long() for x in batched_inputs]
         tr = self.trainer()
-        losses, _aux = tr.forward_backward(frames, gt_boxes, gt_classes, exchange=True)  # (optimizer.step() finishes the exchange)
+        if stage == 2:  # step2_axis.yaml: {loss_cls, loss_box_reg} of the frozen detector + {loss_rot_axis, loss_tran_axis}
+            rot = [x["instances"].gt_rot_axis.float() for x in batched_inputs]
+            tran = [x["instances"].gt_tran_axis.float() for x in batched_inputs]
+            losses, _aux = tr.forward_backward(frames, gt_boxes, gt_classes, rot, tran, exchange=True)
+        else:
+            losses, _aux = tr.forward_backward(frames, gt_boxes, gt_classes, exchange=True)  # (optimizer.step() finishes the exchange)
         names = list(losses)
         outs = _StepLosses.apply(tr.autograd_anchor(), *[losses[k] for k in names])
         return dict(zip(names, outs))
@@ -301,7 +326,7 @@ class PlaneRCNN(nn.Module):
     def train(self, mode: bool = True):
         """Leaving training mode writes the trainer's parameters back into the modules (inference packs its weights from them)."""
         if not mode and getattr(self, "_trainer", None) is not None and self.training:
-            self.load_state_dict(self._trainer.export_state_dict(), strict=False)
+            self.load_state_dict(self._trainer.export_state_dict(), strict=False)  # (stage 2: the axis head's entries only)
         return super().train(mode)
 
     # batches up to this size run the depth decoder on a second HIP stream beside the ROI branch (0 disables: every kernel then runs alone)

@@ -51,8 +51,8 @@ class DeferredReduces:
             return
         sz = C.sizeof(_lib.WgradDesc)
         arr = (_lib.WgradDesc * n)(*self.items)
-        for i in range(n):  # (the reduce reads neither operand: keep the table identical from step to step)
-            arr[i].x = arr[i].dy = None
+        for i in range(n):  # (the reduce reads neither operand nor the live count: keep the table identical from step to step)
+            arr[i].x = arr[i].dy = arr[i].p_dev = None
         raw = C.string_at(C.addressof(arr), n * sz)
         host, dev = self._tables.get(slot, (None, None))
         if raw != host:
@@ -70,9 +70,10 @@ _WGRAD_DESC_CACHE: dict = {}
 
 def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, *, KH: int, KW: int, stride: int, pad: int,
                scale: Optional[torch.Tensor] = None, accumulate: bool = False, splitk: Optional[int] = None, precision: int = 0,
-               defer: Optional[DeferredReduces] = None) -> torch.Tensor:
+               defer: Optional[DeferredReduces] = None, p_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dw [Cout, KH*KW*Cin] (=/+=) weight gradient of y = conv(x) given dy (NHWC tensors).
-    defer: park the slice reduction in a DeferredReduces (one launch for all layers at its flush()); not with accumulate."""
+    defer: park the slice reduction in a DeferredReduces (one launch for all layers at its flush()); not with accumulate.
+    p_dev: device int32, the live output pixels (a multiple of Ho*Wo): images past it are never read (a3d_wgrad_desc.p_dev)."""
     # (precision 1 only: x / dy may be STORED as bf16 -- a3d_wgrad_desc.io_bf16; the kernel rounds them to bf16 anyway)
     _req(x, x.dtype if (precision == 1 and x.dtype == torch.bfloat16) else torch.float32)
     _req(dy, dy.dtype if (precision == 1 and dy.dtype == torch.bfloat16) else torch.float32)
@@ -82,7 +83,8 @@ def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, *, KH: int, 
     assert B == B2 and dw.numel() == Cout * KH * KW * Cin, (x.shape, dy.shape, dw.shape)
     # (the descriptor's static fields, the kernel form and the slice count are functions of the layer and the batch shape: kept per key, only
     # the tensor pointers are written per launch -- host time matters at 2 images per GPU)
-    key = (B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, bool(accumulate), int(precision), x.dtype, dy.dtype, splitk, scale is None, WGRAD_TR_WORKGROUPS, WGRAD_TR_MIN_PIXELS)
+    key = (B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, bool(accumulate), int(precision), x.dtype, dy.dtype, splitk, scale is None, WGRAD_TR_WORKGROUPS, WGRAD_TR_MIN_PIXELS,
+           p_dev is None)
     hit = _WGRAD_DESC_CACHE.get(key)
     if hit is None:
         d = _lib.WgradDesc()
@@ -109,6 +111,8 @@ def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor, *, KH: int, 
     proto, form, nbytes = hit
     d = _lib.WgradDesc.from_buffer_copy(proto)
     d.x, d.dy, d.scale, d.dw = x.data_ptr(), dy.data_ptr(), _p(scale), dw.data_ptr()
+    if p_dev is not None:
+        d.p_dev = _req(p_dev, torch.int32).data_ptr()
     if defer is not None and not accumulate:
         ws = defer.workspace(dw, nbytes)
         d.defer_reduce = 1
@@ -196,6 +200,41 @@ def colsum(dy: torch.Tensor, out: torch.Tensor, accumulate: bool = False) -> tor
         return out
     _lib.check(_lib.lib().a3d_colsum(_p(_req(dy)), _p(out), _p(ws), M, Cc, int(accumulate), _stream()), "a3d_colsum")
     return out
+
+
+def colsum_rows(dy: torch.Tensor, out: torch.Tensor, m_dev: torch.Tensor, accumulate: bool = False) -> torch.Tensor:
+    """out[c] (=/+=) sum over the first *m_dev rows of dy [M, ..., C] (device int32 m_dev): a3d_colsum_rows."""
+    Cc = dy.shape[-1]
+    M = dy.numel() // Cc
+    assert _req(out).numel() >= Cc
+    bf = dy.dtype == torch.bfloat16
+    _req(dy, torch.bfloat16 if bf else torch.float32)
+    ws = torch.empty(_lib.lib().a3d_colsum_workspace_bytes(Cc) // 4, device=dy.device, dtype=torch.float32)
+    _lib.check(_lib.lib().a3d_colsum_rows(_p(dy), int(bf), _p(out), _p(ws), M, _p(_req(m_dev, torch.int32)), Cc, int(accumulate), _stream()),
+               "a3d_colsum_rows")
+    return out
+
+
+def axis_loss(raw_rot: torch.Tensor, raw_tran: torch.Tensor, live: torch.Tensor, row_img: torch.Tensor, row_gt: torch.Tensor,
+              gt_rot_axis: torch.Tensor, gt_tran_axis: torch.Tensor, *, beta: float, loss_weight: float):
+    """The axis loss of the stage-2 step and its gradient (a3d_axis_loss).  raw_rot [rows, >=3] (rotation | offset before F.normalize),
+    raw_tran [rows, >=2]; live: device int32 (rows past it are never read); row_img / row_gt [rows] int32; gt_*_axis [B, max_gt, 4].
+    -> (loss [2] = (loss_rot_axis, loss_tran_axis), d_rot, d_tran) with the raw tensors' shapes (padding columns and dead rows zero)."""
+    rows = _req(raw_rot).shape[0]
+    assert _req(raw_tran).shape[0] == rows and raw_rot.dim() == raw_tran.dim() == 2
+    B, G = _req(gt_rot_axis).shape[:2]
+    assert tuple(_req(gt_tran_axis).shape) == (B, G, 4) and gt_rot_axis.shape[2] == 4
+    d = _lib.AxisLossDesc()
+    loss = torch.empty(2, device=raw_rot.device, dtype=torch.float32)
+    d_rot, d_tran = torch.empty_like(raw_rot), torch.empty_like(raw_tran)
+    d.raw_rot, d.raw_tran, d.live = raw_rot.data_ptr(), raw_tran.data_ptr(), _req(live, torch.int32).data_ptr()
+    d.row_img, d.row_gt = _req(row_img, torch.int32).data_ptr(), _req(row_gt, torch.int32).data_ptr()
+    d.gt_rot_axis, d.gt_tran_axis = gt_rot_axis.data_ptr(), gt_tran_axis.data_ptr()
+    d.loss, d.d_rot, d.d_tran = loss.data_ptr(), d_rot.data_ptr(), d_tran.data_ptr()
+    d.rows, d.rot_pitch, d.tran_pitch, d.B, d.max_gt = rows, raw_rot.shape[1], raw_tran.shape[1], B, G
+    d.beta, d.loss_weight = float(beta), float(loss_weight)
+    _lib.check(_lib.lib().a3d_axis_loss(C.byref(d), _stream()), "a3d_axis_loss")
+    return loss, d_rot, d_tran
 
 
 def roi_align_fpn_backward(dfeats: Sequence[torch.Tensor], scales: Sequence[float], boxes: torch.Tensor, dout: torch.Tensor, *,

@@ -449,9 +449,8 @@ class DetectorTrainer:
             ten.record_stream(main)
         return out, dp6, done
 
-    def _rpn_labels(self, anchors, gt_boxes, gt_classes, samples, seed, B):
-        """Ground truth on the device (fixed-size, counts in a device vector: nothing waits for the host) + the RPN's labels: Matcher + random
-        sub-sampling (256 per image, <= half positive), both on the device.  Depends on the ground truth and the anchor grid only."""
+    def _gt_upload(self, gt_boxes, gt_classes, B):
+        """Ground truth on the device: fixed-size [B, max_gt] tensors, counts in a device vector (nothing waits for the host)."""
         s = self.s
         assert max(len(g) for g in gt_boxes) <= s.max_gt
         gtb = torch.zeros(B, s.max_gt, 4)
@@ -461,7 +460,13 @@ class DetectorTrainer:
             gtb[i, : len(gb)] = gb.cpu()
             gtc[i, : len(gb)] = gc.cpu().to(torch.int32)
             gcount[i] = len(gb)
-        gtb_d, gtc_d, gcount_d = gtb.to(self.dev, non_blocking=True), gtc.to(self.dev, non_blocking=True), gcount.to(self.dev, non_blocking=True)
+        return gtb.to(self.dev, non_blocking=True), gtc.to(self.dev, non_blocking=True), gcount.to(self.dev, non_blocking=True)
+
+    def _rpn_labels(self, anchors, gt_boxes, gt_classes, samples, seed, B):
+        """Ground truth on the device + the RPN's labels: Matcher + random sub-sampling (256 per image, <= half positive), both on the
+        device.  Depends on the ground truth and the anchor grid only."""
+        s = self.s
+        gtb_d, gtc_d, gcount_d = self._gt_upload(gt_boxes, gt_classes, B)
         midx, lab = T.match_boxes(anchors, gtb_d, gcount_d, thresholds=s.rpn_iou_thresholds, labels=(0, -1, 1), allow_low_quality=True,
                                   shared=True)
         if samples is None:
@@ -553,13 +558,32 @@ class DetectorTrainer:
         finally:
             ops.BF16_SPLITK_AUTO = saved
 
-    def _forward_backward(self, frames_u8, gt_boxes, gt_classes, samples):
+    def frozen_forward(self, frames_u8: torch.Tensor, gt_boxes: Sequence[torch.Tensor], gt_classes: Sequence[torch.Tensor],
+                       samples: Optional[dict] = None) -> Tuple[Dict[str, torch.Tensor], dict]:
+        """The forward half of `forward_backward` for a later training stage that freezes this whole detector (config/step2_axis.yaml:
+        FREEZE backbone, proposal_generator, box head and predictor): the same launches in the same precision and storage, with the same
+        ROI sampling seed, so proposals, sampled index sets, classes and box losses are those `forward_backward` computes -- without the
+        anchor labelling, the RPN loss, any kept activation or backward launch.  The parameters never change here, so the filters are
+        prepared once.  -> ({loss_cls, loss_box_reg}, aux: pyramid, sampled ROIs, their matches, ground truth on the device)."""
+        saved, ops.BF16_SPLITK_AUTO = ops.BF16_SPLITK_AUTO, True
+        self._cur_stream, self._wg_calls = torch.cuda.current_stream(), 0
+        if not hasattr(self, "_wg_events"):
+            self._wg_events = []
+        self._xchg_live, self._late = False, []
+        try:
+            return self._forward_backward(frames_u8, gt_boxes, gt_classes, samples, frozen=True)
+        finally:
+            ops.BF16_SPLITK_AUTO = saved
+
+    def _forward_backward(self, frames_u8, gt_boxes, gt_classes, samples, frozen=False):
         s, L, m = self.s, self.layers, self.model
         B, H, W, _ = frames_u8.shape
         # The per-step filter preparation (data-gradient transposes, bf16 copies: three HBM-bound launches over all parameters) does not touch
         # the frozen stem / res2, so it runs on the side stream beside their forward pass; res3's first launch waits for it.
         prepared = None
-        if self._wg_stream is not None:
+        if frozen and getattr(self, "_frozen_prepared", False):
+            pass  # (frozen: the parameters have not changed since the last preparation)
+        elif self._wg_stream is not None:
             main, side = self._cur_stream, self._wg_stream
             ev = self._next_event()
             ev.record(main)  # (behind the previous step's optimiser update)
@@ -575,9 +599,10 @@ class DetectorTrainer:
                 self._cur_stream = main
         else:
             self._prepare_filters()
+        self._frozen_prepared = frozen
         seed = (self.seed * 1000003 + self.iter) * 4
         labels_early, early_hw = None, None
-        if self._rpn_stream is not None:  # ground-truth upload, anchor matching and label sampling: beside the backbone's forward pass
+        if self._rpn_stream is not None and not frozen:  # ground-truth upload, anchor matching and label sampling: beside the backbone's forward pass
             early_hw, labels_early = self._rpn_labels_early(H, W, gt_boxes, gt_classes, samples, seed, B)
         saved = {}
         relu_outputs = []  # every ReLU output on the trainable path, in forward order (aux: lets a checker reuse the gates)
@@ -596,8 +621,9 @@ class DetectorTrainer:
                 a = self._conv(x, L[p + "conv1"].fwd(), out_dtype=st)
                 b = self._conv(a, L[p + "conv2"].fwd(), out_dtype=st)
                 out = self._conv(b, L[p + "conv3"].fwd(), res=sc, out_dtype=st)
-                saved[p] = (x, a, b)
-                relu_outputs += [a, b, out]
+                if not frozen:
+                    saved[p] = (x, a, b)
+                    relu_outputs += [a, b, out]
                 x = out
             res[name] = x
         # ---- FPN
@@ -664,15 +690,18 @@ class DetectorTrainer:
         heads = [hmap[n] for n in names]
         feat_hw = [tuple(feats[n].shape[1:3]) for n in names]
         anchors = self._anchors(feat_hw)
-        if labels_early is None:
+        if frozen:  # (no anchor labels: the RPN loss is dropped with the RPN frozen)
+            gtb_d, gtc_d, gcount_d = self._gt_upload(gt_boxes, gt_classes, B)
+        elif labels_early is None:
             gtb_d, gtc_d, gcount_d, midx, lab, labels_d = self._rpn_labels(anchors, gt_boxes, gt_classes, samples, seed, B)
         else:  # (matched and sampled on the second stream while the backbone ran)
             assert tuple(feat_hw) == tuple(early_hw), (feat_hw, early_hw)
             gtb_d, gtc_d, gcount_d, midx, lab, labels_d, ready = labels_early
             self._cur_stream.wait_event(ready)
-        rpn_l, dheads = T.rpn_loss(heads, self.strides, self.cell_anchors, labels_d, midx, gtb_d, A=3, weights=s.rpn_weights,
-                                   normalizer=float(s.rpn_batch_per_image * B))
-        early = self._rpn_head_backward_early(names, dheads, t, feats, st) if self._rpn_stream is not None else None
+        if not frozen:
+            rpn_l, dheads = T.rpn_loss(heads, self.strides, self.cell_anchors, labels_d, midx, gtb_d, A=3, weights=s.rpn_weights,
+                                       normalizer=float(s.rpn_batch_per_image * B))
+            early = self._rpn_head_backward_early(names, dheads, t, feats, st) if self._rpn_stream is not None else None
         # ---- proposals (no gradient) + ground truth, Matcher, sub-sampling (512 per image, <= a quarter foreground)
         pb, _ps, _lvl, _pos, pcount = ops.rpn_proposals(heads, self.strides, self.cell_anchors, (H, W), pre_topk=s.rpn_pre_topk_train,
                                                         post_topk=s.rpn_post_topk_train, nms_thresh=s.rpn_nms_thresh, min_size=0.0,
@@ -711,6 +740,10 @@ class DetectorTrainer:
         pred = self._conv(h2, L[bp + "pred"].fwd())
         box_l, dpred = T.box_loss(pred.view(M, 32), roi_cls.view(M), roi_boxes.view(M, 4), roi_gt.view(M, 4), num_classes=s.num_classes,
                                   weights=s.box_weights, count=rcount_d, rows_per_image=Rs)
+        if frozen:
+            return {"loss_cls": box_l[0], "loss_box_reg": box_l[1]}, dict(
+                feats=feats, proposals=(pb, pcount), roi_boxes=roi_boxes, roi_cls=roi_cls, roi_index=roi_index, roi_count=rcount_d,
+                proposal_match=pmidx, gt=(gtb_d, gtc_d, gcount_d), pred=pred.view(M, 32))
         losses = {"loss_rpn_cls": rpn_l[0], "loss_rpn_loc": rpn_l[1], "loss_cls": box_l[0], "loss_box_reg": box_l[1]}
 
         # ======================================== backward ========================================

@@ -34,8 +34,8 @@ extern "C" {
 int a3d_version(void);
 /* sizeof() of a descriptor struct, for bindings to verify their mirror of the layout.  id: 0 a3d_conv_desc, 1 a3d_rpn_desc,
  * 2 a3d_boxdet_desc, 3 a3d_roialign_desc, 4 a3d_paste_desc, 5 a3d_pack_desc, 6 a3d_wgrad_desc, 7 a3d_roialign_bwd_desc,
- * 8 a3d_match_desc, 9 a3d_rpn_loss_desc, 10 a3d_box_loss_desc, 11 a3d_roi_sample_desc, 12 a3d_sweep_desc, 13 a3d_transpose_item; 0 for an
- * unknown id. */
+ * 8 a3d_match_desc, 9 a3d_rpn_loss_desc, 10 a3d_box_loss_desc, 11 a3d_roi_sample_desc, 12 a3d_sweep_desc, 13 a3d_transpose_item,
+ * 14 a3d_axis_loss_desc; 0 for an unknown id. */
 size_t a3d_struct_size(int id);
 
 /* ------------------------------------------------------------------------------------------------
@@ -477,6 +477,9 @@ typedef struct a3d_wgrad_desc {
     int defer_reduce;   /* 1: launch the partial-sum kernel only; the caller keeps `workspace` alive and folds the slices of MANY layers
                            in one launch later (a3d_wgrad_reduce_batch).  Same sums in the same order: bit-identical dw.  Not with
                            accumulate (a chain of launches into one dw is ordered by its reduces).                                  */
+    const int *p_dev;   /* optional DEVICE int: the live output-pixel count, a multiple of Ho*Wo and <= B*Ho*Wo (ragged per-ROI batches,
+                           rows compacted to the front).  Pixels past it are never read; the `splitk` slices divide the LIVE pixels.
+                           NULL, or a count equal to B*Ho*Wo, gives the bits of the full reduction.                                  */
 } a3d_wgrad_desc;
 size_t a3d_wgrad_workspace_bytes(const a3d_wgrad_desc *d);
 int a3d_conv_wgrad_nhwc_f32(const a3d_wgrad_desc *d, void *stream);
@@ -516,6 +519,37 @@ int a3d_colsum(const float *dy, float *out, float *workspace, int M, int C, int 
 /* dy stored as bf16 (the bf16 training step keeps its activation gradients that way): the same sums, in the same order, as a3d_colsum on
  * the widened values.  C % 4 == 0. */
 int a3d_colsum_bf16(const void *dy, float *out, float *workspace, int M, int C, int accumulate, void *stream);
+/* The same over the first *m_dev rows of dy only (m_dev: DEVICE int, <= M; ragged per-ROI batches): rows past it are never read, the
+ * slices divide the live rows.  bf16: dy stored as bf16.  C % 4 == 0, dy 16-byte (bf16: 8-byte) aligned. */
+int a3d_colsum_rows(const void *dy, int bf16, float *out, float *workspace, int M, const int *m_dev, int C, int accumulate, void *stream);
+
+/* Axis loss of the articulation head's training stage (config/step2_axis.yaml; pkg/modeling/roi_heads/axis_head.py:95-201), forward AND
+ * backward in one launch.  Rows are the compacted foreground ROIs [0, *live).  Per live row r: image row_img[r], matched ground truth
+ * row_gt[r] -> gt_rot = gt_rot_axis[img][g] / gt_tran = gt_tran_axis[img][g], each [sin, cos, offset, valid].
+ *   rot  = [normalize(raw_rot[r,0:2]), raw_rot[r,2]],   loss_rot  = W * mean over valid rows' 3 elements of smooth_l1(rot - gt_rot[0:3])
+ *   tran = normalize(raw_tran[r,0:2]),                   loss_tran = W * mean over valid rows' 2 elements of
+ *                                                                     smooth_l1(double_angle(tran) - double_angle(gt_tran[0:2]))
+ * normalize: v / max(|v|, 1e-12) (F.normalize); double_angle(s, c) = (2sc, c^2 - s^2); valid: [3] >= 0.5; a loss whose valid column sums
+ * below 1 is 0 with zero gradients (the reference's early return).  smooth_l1 with beta < 1e-5 is |x| (gradient sign(x), 0 at 0).
+ * Outputs: loss[2] = (loss_rot, loss_tran); d_rot [rows,3] / d_tran [rows,2] = gradients of (loss_rot + loss_tran) with respect to the raw
+ * rows, dead rows written as zeros.  One workgroup, fixed summation order, no atomics: bit-reproducible. */
+typedef struct a3d_axis_loss_desc {
+    const float *raw_rot;       /* [rows,rot_pitch]: rotation (2) | offset (1) */
+    const float *raw_tran;      /* [rows,tran_pitch] */
+    const int *live;            /* DEVICE int: live rows (<= rows) */
+    const int *row_img;         /* [rows] */
+    const int *row_gt;          /* [rows] */
+    const float *gt_rot_axis;   /* [B, max_gt, 4] */
+    const float *gt_tran_axis;  /* [B, max_gt, 4] */
+    float *loss;                /* [2] */
+    float *d_rot;               /* [rows,rot_pitch]: columns 3.. written as zeros */
+    float *d_tran;              /* [rows,tran_pitch]: columns 2.. written as zeros */
+    int rows;
+    int rot_pitch, tran_pitch;  /* row pitch (floats) of raw_rot / d_rot (>= 3) and raw_tran / d_tran (>= 2) */
+    int B, max_gt;
+    float beta, loss_weight;
+} a3d_axis_loss_desc;
+int a3d_axis_loss(const a3d_axis_loss_desc *d, void *stream);
 
 /* Gradient of a3d_roi_align_fpn with respect to the pyramid: dfeat[level] += scatter(dout).  dfeat must hold the
  * gradient accumulated so far (or zeros).  Adaptive sampling (sampling_ratio 0) only: the box pooler. */
