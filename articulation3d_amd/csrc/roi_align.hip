@@ -168,7 +168,14 @@ __global__ __launch_bounds__(64 * NW, H2 ? 3 : 1) void roi_align_fpn_kernel(cons
     constexpr int KMAX = 16, PMAX = 16;
     __shared__ float WY[PMAX][KMAX], WX[PMAX][KMAX];
     __shared__ int Y0[PMAX], NY[PMAX], X0[PMAX], NX[PMAX];
-    const bool separable = gh < KMAX && gw < KMAX && a.P <= PMAX;  // uniform per workgroup
+    // A table row holds the KMAX cells from the first sample's low cell on.  Adaptive lattices (ratio 0: g = ceil(bin size)) put their
+    // samples at most one cell apart, so g < KMAX samples span at most g cells.  A FIXED ratio does not: its samples lie bsz / g cells
+    // apart whatever the bin size (the mask pooler's 2 x 2 lattice on a 30-cell bin: 15 cells between the two samples, hi - base = 16).
+    // First to last sample are d = (g - 1) * bsz / g cells apart, so last - base <= floor(d) + 2; the table path is taken while
+    // d + 3 < KMAX (one cell of slack for the fp32 rounding of the coordinates) and wider bins go to the per-sample path below.
+    // The condition is a function of the ROI alone, computed by every thread before any table entry is written.
+    const bool fits = a.ratio <= 0 || ((float)(gh - 1) * (bh / (float)gh) + 3.0f < (float)KMAX && (float)(gw - 1) * (bw / (float)gw) + 3.0f < (float)KMAX);
+    const bool separable = gh < KMAX && gw < KMAX && a.P <= PMAX && fits;  // uniform per workgroup
     if (separable) {
         if (threadIdx.x < 2 * a.P) {
             const bool isx = threadIdx.x >= a.P;
