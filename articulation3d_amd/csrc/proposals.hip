@@ -18,6 +18,7 @@ typedef unsigned long long u64;
 
 __device__ __forceinline__ uint32_t ordered_key(float f) {
     f = f + 0.0f;  // -0 -> +0 so that equal floats give equal keys
+    if (f != f) return 0xffffffffu;  // every NaN, whatever its sign bit or payload, sorts first (torch.sort) -- one key, so NaNs tie by index
     const uint32_t u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
@@ -60,8 +61,8 @@ __device__ __forceinline__ void decode_clip(const float ax1, const float ay1, co
     dy = dy / wy;
     dw = dw / ww;
     dh = dh / wh;
-    dw = fminf(dw, clampv);
-    dh = fminf(dh, clampv);
+    dw = dw > clampv ? clampv : dw;  // torch.clamp(max=): a NaN stays a NaN (fminf would drop it and make the box finite)
+    dh = dh > clampv ? clampv : dh;
     const float pcx = dx * w + cx, pcy = dy * h + cy;
     const float pw = expf(dw) * w, ph = expf(dh) * h;
     float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;

@@ -1355,6 +1355,18 @@ def group_workspace(n_groups: int, device) -> torch.Tensor:
     return torch.empty(_lib.lib().a3d_group_buffers_bytes(n_groups), device=device, dtype=torch.uint8)
 
 
+def _selection_workspace(workspace, nbytes: int, device) -> torch.Tensor:
+    """The workspace of a selection launch: a fresh one, or the caller's when it is large enough (the kernels read no byte of it
+    that the same launch has not written)."""
+    if workspace is None:
+        return torch.empty(nbytes, device=device, dtype=torch.uint8)
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != torch.device(device):
+        raise ValueError("workspace: a contiguous uint8 tensor on the launch's device is needed")
+    if workspace.numel() < nbytes or workspace.data_ptr() % 16:  # (the only guard between a short buffer and the kernels' writes)
+        raise ValueError(f"workspace: {workspace.numel()} bytes at {workspace.data_ptr():#x}, {nbytes} bytes 16-byte aligned are needed")
+    return workspace
+
+
 def carve_group_workspace(ws: torch.Tensor, G: int) -> dict:
     """Views of the selection workspace (layout of `carve()` in csrc/proposals.hip): per group the
     score-sorted candidate boxes, scores, tie-break positions, validity and NMS keep flags.  Test hook."""
@@ -1373,9 +1385,10 @@ def carve_group_workspace(ws: torch.Tensor, G: int) -> dict:
 
 def rpn_proposals(heads: Sequence[torch.Tensor], strides: Sequence[int], cell_anchors: torch.Tensor, img_hw, *,
                   pre_topk: int, post_topk: int, nms_thresh: float, min_size: float, weights, scale_clamp: float,
-                  return_groups: bool = False):
+                  return_groups: bool = False, workspace: Optional[torch.Tensor] = None):
     """heads[l]: [B,Hf,Wf,CH] (objectness 0..A-1, deltas A..5A-1).  cell_anchors: CPU float32 [L,3,4].
-    -> boxes [B,post,4], logits [B,post], level [B,post] int32, pos [B,post] int32, count [B] int32."""
+    -> boxes [B,post,4], logits [B,post], level [B,post] int32, pos [B,post] int32, count [B] int32.
+    workspace: a caller-owned uint8 tensor of at least a3d_rpn_workspace_bytes(B, L, pre_topk) bytes to run in (its contents do not matter)."""
     L = len(heads)
     B = heads[0].shape[0]
     dev = heads[0].device
@@ -1394,11 +1407,9 @@ def rpn_proposals(heads: Sequence[torch.Tensor], strides: Sequence[int], cell_an
     for j in range(4):
         d.weights[j] = float(weights[j])
     d.scale_clamp = float(scale_clamp)
-    if pre_topk <= GROUP_CAP:
-        ws = group_workspace(B * L, dev)
-    else:  # training's 2000 candidates per level: 2048-slot groups + global NMS words
-        assert not return_groups, "group buffers are only exposed in the 1024-slot layout"
-        ws = torch.empty(_lib.lib().a3d_rpn_workspace_bytes(B, L, int(pre_topk)), device=dev, dtype=torch.uint8)
+    assert pre_topk <= GROUP_CAP or not return_groups, "group buffers are only exposed in the 1024-slot layout"
+    # (pre_topk > 1024 is training's 2000 candidates per level: 2048-slot groups + global NMS words)
+    ws = _selection_workspace(workspace, _lib.lib().a3d_rpn_workspace_bytes(B, L, int(pre_topk)), dev)
     boxes = torch.empty((B, post_topk, 4), device=dev, dtype=torch.float32)
     scores = torch.empty((B, post_topk), device=dev, dtype=torch.float32)
     level = torch.empty((B, post_topk), device=dev, dtype=torch.int32)
@@ -1415,8 +1426,9 @@ def rpn_proposals(heads: Sequence[torch.Tensor], strides: Sequence[int], cell_an
 
 def box_detections(pred: torch.Tensor, prop_boxes: torch.Tensor, prop_count: torch.Tensor, img_hw, *, num_classes: int,
                    score_thresh: float, nms_thresh: float, topk: int, weights, scale_clamp: float,
-                   return_groups: bool = False):
-    """pred [B*R, CH] (cls logits 0..C, deltas C+1..), prop_boxes [B,R,4], prop_count [B] int32."""
+                   return_groups: bool = False, workspace: Optional[torch.Tensor] = None):
+    """pred [B*R, CH] (cls logits 0..C, deltas C+1..), prop_boxes [B,R,4], prop_count [B] int32.
+    workspace: a caller-owned uint8 tensor of at least a3d_group_buffers_bytes(B * num_classes) bytes to run in."""
     _req(pred)
     _req(prop_boxes)
     _req(prop_count, torch.int32)
@@ -1430,7 +1442,7 @@ def box_detections(pred: torch.Tensor, prop_boxes: torch.Tensor, prop_count: tor
     for j in range(4):
         d.weights[j] = float(weights[j])
     d.scale_clamp = float(scale_clamp)
-    ws = group_workspace(B * num_classes, dev)
+    ws = _selection_workspace(workspace, _lib.lib().a3d_group_buffers_bytes(B * num_classes), dev)
     boxes = torch.empty((B, topk, 4), device=dev, dtype=torch.float32)
     scores = torch.empty((B, topk), device=dev, dtype=torch.float32)
     classes = torch.empty((B, topk), device=dev, dtype=torch.int32)
