@@ -60,7 +60,8 @@ def _hipcc() -> str:
 
 def _stamp(path: str, flags) -> str:
     h = hashlib.sha1()
-    for p in (path, os.path.join(CSRC, "a3d_common.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(PKG_DIR, "..", "include", "a3d.h")):
+    headers = sorted(os.path.join(CSRC, n) for n in os.listdir(CSRC) if n.endswith(".h"))
+    for p in (path, *headers, os.path.join(PKG_DIR, "..", "include", "a3d.h")):
         with open(p, "rb") as f:
             h.update(f.read())
     h.update(" ".join(COMMON + list(flags)).encode())

@@ -16,15 +16,7 @@
 #include <stdlib.h>
 
 namespace {
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ f32x4 bf_load4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t bf_rsrc(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
 // bf16 STORAGE (a3d_conv_desc.io_bf16): four stored bf16 values <-> f32x4.  Widening is exact; narrowing rounds to nearest even.
 typedef unsigned int bf_u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x4 bf_widen4(const bf_u32x2 v) {
@@ -76,8 +68,8 @@ __global__ __launch_bounds__(256, 3) void conv_bf16_kernel(const a3d_conv_desc d
     const int lrx = tid / TPRX, lcx = (tid % TPRX) * XE;
     const bool yb = d.io_bf16 & 2, rb = d.io_bf16 & 4, gb = d.io_bf16 & 8;  // tensors stored as bf16
     const int cs4 = d.Cin * XES;  // bytes per input pixel
-    const __amdgpu_buffer_rsrc_t rx = bf_rsrc(d.x, (unsigned)((size_t)d.B * d.H * d.W * (size_t)cs4));
-    const __amdgpu_buffer_rsrc_t rw = bf_rsrc(d.w, (unsigned)((size_t)d.Cout * d.Kpad * 4));
+    const __amdgpu_buffer_rsrc_t rx = a3d_rsrc(d.x, (unsigned)((size_t)d.B * d.H * d.W * (size_t)cs4));
+    const __amdgpu_buffer_rsrc_t rw = a3d_rsrc(d.w, (unsigned)((size_t)d.Cout * d.Kpad * 4));
 
     int rowoff[XR];
     unsigned vmask[XR];
@@ -118,11 +110,11 @@ __global__ __launch_bounds__(256, 3) void conv_bf16_kernel(const a3d_conv_desc d
 #pragma unroll
         for (int i = 0; i < XR; ++i) {
             const bool on = (vmask[i] >> (tap & 31)) & livebit;
-            xs[i] = bf_load4(rx, on ? rowoff[i] + tapoff : -1, 0);  // (XB: the four dwords are 8 stored bf16 values)
+            xs[i] = a3d_load4(rx, on ? rowoff[i] + tapoff : -1, 0);  // (XB: the four dwords are 8 stored bf16 values)
         }
         const int soff = (k_first + kc) * (BKT * 4);
 #pragma unroll
-        for (int i = 0; i < WR; ++i) ws[i] = bf_load4(rw, livebit ? woff[i] : -1, soff);
+        for (int i = 0; i < WR; ++i) ws[i] = a3d_load4(rw, livebit ? woff[i] : -1, soff);
         ++kc;
         c0 += BKT;
         if (c0 >= d.Cin) {

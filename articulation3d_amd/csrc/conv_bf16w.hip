@@ -19,20 +19,8 @@
 #include "conv_common.h"
 
 namespace {
-typedef __bf16 bw_bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bw_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float bw_f32x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int bw_u32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t bw_rsrc(const void *p, unsigned bytes) {
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    void *q = reinterpret_cast<void *>(((unsigned long long)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(q, 0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-__device__ __forceinline__ void bw_dma16(__amdgpu_buffer_rsrc_t r, void *lds_dst, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)lds_dst, 16, voff, soff, 0, 0);
-}
 __device__ __forceinline__ f32x4 bw_widen4(const bw_u32x2 v) {
     f32x4 o;
     o[0] = __builtin_bit_cast(float, v[0] << 16);
@@ -46,7 +34,7 @@ __device__ __forceinline__ f32x4 bw_read4(const float *base, size_t idx, bool is
     return *reinterpret_cast<const f32x4 *>(base + idx);
 }
 __device__ __forceinline__ void bw_write4(float *base, size_t idx, const f32x4 v, bool is_bf16) {
-    if (is_bf16) *reinterpret_cast<bw_bf16x4 *>(reinterpret_cast<__bf16 *>(base) + idx) = __builtin_convertvector(v, bw_bf16x4);
+    if (is_bf16) *reinterpret_cast<bf16x4 *>(reinterpret_cast<__bf16 *>(base) + idx) = __builtin_convertvector(v, bf16x4);
     else *reinterpret_cast<f32x4 *>(base + idx) = v;
 }
 
@@ -83,7 +71,7 @@ __global__ __launch_bounds__(512, 2) void conv_bf16w_kernel(const a3d_conv_desc 
     // ---- activation DMA.  Piece j of this wave = tile rows (wave XPW + j) RPP .. + RPP - 1; lane i -> row i / (64 / RPP), LDS slot
     // i % (64 / RPP), which keeps the row's global 16-byte slot  slot ^ swizzle(row): 64-byte rows (row >> 2) & 3, 128-byte rows
     // (row >> 1) & 7 -- the fragment reads below are conflict-free with either.
-    const __amdgpu_buffer_rsrc_t rx = bw_rsrc(d.x, (unsigned)((size_t)d.B * d.H * d.W * d.Cin * ES));
+    const __amdgpu_buffer_rsrc_t rx = a3d_rsrc_uniform(d.x, (unsigned)((size_t)d.B * d.H * d.W * d.Cin * ES));
     int xoff[XPW];
     unsigned xmask[XPW];
 #pragma unroll
@@ -106,7 +94,7 @@ __global__ __launch_bounds__(512, 2) void conv_bf16w_kernel(const a3d_conv_desc 
         xmask[j] = mask;
     }
     // ---- filter DMA: w_bf16 [Cout][Kpad] bf16; piece j of this wave = tile rows (wave WPW + j) 16 .. + 15, 64 bytes of chunk c each
-    const __amdgpu_buffer_rsrc_t rw = bw_rsrc(d.w_bf16, (unsigned)((size_t)d.Cout * d.Kpad * 2));
+    const __amdgpu_buffer_rsrc_t rw = a3d_rsrc_uniform(d.w_bf16, (unsigned)((size_t)d.Cout * d.Kpad * 2));
     int woff[WPW];
 #pragma unroll
     for (int j = 0; j < WPW; ++j) {
@@ -123,10 +111,10 @@ __global__ __launch_bounds__(512, 2) void conv_bf16w_kernel(const a3d_conv_desc 
         const int tapoff = __builtin_amdgcn_readfirstlane(((kh * d.W + kw) * d.Cin + dc0) * ES);
 #pragma unroll
         for (int j = 0; j < XPW; ++j)
-            bw_dma16(rx, X + (wave * XPW + j) * 1024, (live && ((xmask[j] >> dtap) & 1u)) ? xoff[j] + tapoff : -1, 0);
+            a3d_dma16(rx, X + (wave * XPW + j) * 1024, (live && ((xmask[j] >> dtap) & 1u)) ? xoff[j] + tapoff : -1, 0);
         const int wsoff = __builtin_amdgcn_readfirstlane(dma_c * 64);
 #pragma unroll
-        for (int j = 0; j < WPW; ++j) bw_dma16(rw, Wt + (wave * WPW + j) * 1024, (live && woff[j] >= 0) ? woff[j] + wsoff : -1, 0);
+        for (int j = 0; j < WPW; ++j) a3d_dma16(rw, Wt + (wave * WPW + j) * 1024, (live && woff[j] >= 0) ? woff[j] + wsoff : -1, 0);
         ++dma_c;
         dc0 += BW_BK;
         if (dc0 >= d.Cin) {
@@ -139,7 +127,7 @@ __global__ __launch_bounds__(512, 2) void conv_bf16w_kernel(const a3d_conv_desc 
     // ---- fragments: row = lane % 32 of a 32-row block, k = 8 (lane / 32) .. + 7 of a 16-deep step
     const int frow = lane & 31;
     const int sw4 = (frow >> 2) & 3, sw8 = (frow >> 1) & 7;  // (block row offsets are multiples of 32: a row's swizzle is that of lane % 32)
-    bw_bf16x8 fa[2][TN], fb[2][TM];
+    bf16x8 fa[2][TN], fb[2][TM];
     auto rd_all = [&](const int st) {
         const unsigned char *X = bw_lds + st * STAGE;
         const unsigned char *Wt = X + XBYTES;
@@ -148,17 +136,17 @@ __global__ __launch_bounds__(512, 2) void conv_bf16w_kernel(const a3d_conv_desc 
             const int g = 2 * s2 + (lane >> 5);  // the fragment's 16-byte slot of a 64-byte row
 #pragma unroll
             for (int n = 0; n < TN; ++n)
-                fa[s2][n] = *reinterpret_cast<const bw_bf16x8 *>(Wt + ((wn * TN + n) * 32 + frow) * 64 + ((g ^ sw4) << 4));
+                fa[s2][n] = *reinterpret_cast<const bf16x8 *>(Wt + ((wn * TN + n) * 32 + frow) * 64 + ((g ^ sw4) << 4));
 #pragma unroll
             for (int mi = 0; mi < TM; ++mi) {
                 const int row = (wm * TM + mi) * 32 + frow;
                 if constexpr (XB) {
-                    fb[s2][mi] = *reinterpret_cast<const bw_bf16x8 *>(X + row * 64 + ((g ^ sw4) << 4));
+                    fb[s2][mi] = *reinterpret_cast<const bf16x8 *>(X + row * 64 + ((g ^ sw4) << 4));
                 } else {  // fp32-stored: the 8 k values are two slots of the 128-byte row; rounded to bf16 here (nearest even)
                     const f32x4 lo = *reinterpret_cast<const f32x4 *>(X + row * 128 + (((2 * g) ^ sw8) << 4));
                     const f32x4 hi = *reinterpret_cast<const f32x4 *>(X + row * 128 + (((2 * g + 1) ^ sw8) << 4));
-                    const bw_f32x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                    fb[s2][mi] = __builtin_convertvector(v, bw_bf16x8);
+                    const f32x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                    fb[s2][mi] = __builtin_convertvector(v, bf16x8);
                 }
             }
         }
@@ -188,7 +176,7 @@ __global__ __launch_bounds__(512, 2) void conv_bf16w_kernel(const a3d_conv_desc 
     // ---- prologue: the ring filled, chunk 0 landed
 #pragma unroll
     for (int i = 0; i < NST; ++i) dma(i);
-    __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 1) * OPS) : "memory");
+    a3d_wait_vm<(NST - 1) * OPS>();
     __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     // ---- ping-pong loop: waves 0-3 run memory, compute, BARRIER and waves 4-7 memory, BARRIER, compute.  Between BAR_c and BAR_c+1 every wave
@@ -201,12 +189,12 @@ __global__ __launch_bounds__(512, 2) void conv_bf16w_kernel(const a3d_conv_desc 
         if (it > 0) dma(stp);
         __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (grpB) {
-            __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * OPS) : "memory");
+            a3d_wait_vm<(NST - 2) * OPS>();
             __builtin_amdgcn_s_barrier();
         }
         compute();
         if (!grpB) {
-            __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * OPS) : "memory");
+            a3d_wait_vm<(NST - 2) * OPS>();
             __builtin_amdgcn_s_barrier();
         }
         stp = st;

@@ -21,34 +21,6 @@
 #include <stdlib.h>
 
 namespace {
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x4 x3_load4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t x3_rsrc(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-// fp16x2 mode (a3d_conv_desc.precision == 3): x * s = h + l with h, l fp16 and s a power of two that puts the tensor's largest
-// magnitude in [2^14, 2^15): h carries 11 significant bits, l the next 11 (2^-22 relative wherever |x| >= max / 2^18, 2^-40 of the
-// maximum below); h.h + h.l + l.h with fp32 accumulation drops only l.l (<= 2^-22 relative).  THREE MFMAs per k step.
-__device__ __forceinline__ void split2h(const f32x4 v, const float s, h16x4 &h, h16x4 &l) {
-    const f32x4 xs = v * s;
-    h = __builtin_convertvector(xs, h16x4);
-    const f32x4 r = xs - __builtin_convertvector(h, f32x4);
-    l = __builtin_convertvector(r, h16x4);
-}
-// x = h + m + l exactly (round-to-nearest-even at each level)
-__device__ __forceinline__ void split3(const f32x4 v, bf16x4 &h, bf16x4 &m, bf16x4 &l) {
-    h = __builtin_convertvector(v, bf16x4);
-    const f32x4 r1 = v - __builtin_convertvector(h, f32x4);
-    m = __builtin_convertvector(r1, bf16x4);
-    const f32x4 r2 = r1 - __builtin_convertvector(m, f32x4);
-    l = __builtin_convertvector(r2, bf16x4);
-}
 
 // STEM: the 7x7 s2 p3 stem on the NHWC4 input (a3d_conv_desc.stem; w packed [Cout][7][8][4], Kpad = 224): a 16-deep chunk is 4
 // consecutive filter columns x 4 channels of one filter row, i.e. loader lane j = tid % 4 fetches pixel (ih0 + kh, iw0 + 4 (c & 1) + j)
@@ -89,9 +61,9 @@ __global__ __launch_bounds__(256, 3) void conv_x3_kernel(const a3d_conv_desc d, 
     const int lcs = (lc & 7) | ((((lc >> 3) ^ (lr >> 3)) & 1) << 3);
     const int cs4 = STEM ? 16 : d.Cin * 4;
     const int CinT = d.Cin + d.Cin2;  // (a second source has the same channel count: checked by the launcher)
-    const __amdgpu_buffer_rsrc_t rx = x3_rsrc(d.x, (unsigned)((size_t)d.B * d.H * d.W * (size_t)cs4));
-    const __amdgpu_buffer_rsrc_t rx2 = x3_rsrc(d.x2 ? d.x2 : d.x, (unsigned)((size_t)d.B * d.H * d.W * (size_t)cs4));
-    const __amdgpu_buffer_rsrc_t rw = x3_rsrc(d.w, (unsigned)((size_t)d.Cout * d.Kpad * 4));
+    const __amdgpu_buffer_rsrc_t rx = a3d_rsrc(d.x, (unsigned)((size_t)d.B * d.H * d.W * (size_t)cs4));
+    const __amdgpu_buffer_rsrc_t rx2 = a3d_rsrc(d.x2 ? d.x2 : d.x, (unsigned)((size_t)d.B * d.H * d.W * (size_t)cs4));
+    const __amdgpu_buffer_rsrc_t rw = a3d_rsrc(d.w, (unsigned)((size_t)d.Cout * d.Kpad * 4));
 
     const float sw = F16 ? d.w_scale : 1.f;  // weight scale of the fp16x2 split; the activation rows carry their image's scale:
     float sxr[XR];
@@ -135,7 +107,7 @@ __global__ __launch_bounds__(256, 3) void conv_x3_kernel(const a3d_conv_desc d, 
     // WDMA: w_x3 [Kpad/16][2][Cout][16] fp16; one (chunk, plane) tile of this workgroup's BN rows is a contiguous run = BN / 32 DMA
     // wave-instructions of 32 rows.  Lane i lands at LDS byte 16 i of its 1 KiB = row i/2, half i%2, and fetches the k half the image
     // keeps there: half ^ ((row >> 3) & 1).  Rows past Cout read the next plane's rows / zeros: their accumulators are never stored.
-    const __amdgpu_buffer_rsrc_t rw2 = x3_rsrc(WDMA ? d.w_x3 : d.w, WDMA ? (unsigned)((size_t)nk * d.Cout * 64) : 16u);
+    const __amdgpu_buffer_rsrc_t rw2 = a3d_rsrc(WDMA ? d.w_x3 : d.w, WDMA ? (unsigned)((size_t)nk * d.Cout * 64) : 16u);
     const int wvoff = (lane >> 1) * 32 + (((lane & 1) ^ ((lane >> 4) & 1)) << 4);
     int dma_c = 0;
     constexpr int NPC = 2 * (BN / 32);      // DMA pieces per chunk
@@ -151,8 +123,7 @@ __global__ __launch_bounds__(256, 3) void conv_x3_kernel(const a3d_conv_desc d, 
             const int j = uw * DPWN + i;
             if (j < NPC) {
                 const int p = j / (BN / 32), g = j % (BN / 32);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw2, (__attribute__((address_space(3))) void *)(Wt + p * PW + g * 32 * LKB), 16, wvoff,
-                                                         base + __builtin_amdgcn_readfirstlane(p * d.Cout * 32 + g * 1024), 0, 0);
+                a3d_dma16(rw2, Wt + p * PW + g * 32 * LKB, wvoff, base + __builtin_amdgcn_readfirstlane(p * d.Cout * 32 + g * 1024));
             }
         }
         ++dma_c;
@@ -173,11 +144,11 @@ __global__ __launch_bounds__(256, 3) void conv_x3_kernel(const a3d_conv_desc d, 
             const int tapoff = (skh * d.W + half * 4) * 16;
 #pragma unroll
             for (int i = 0; i < XR; ++i)
-                xs[i] = x3_load4(rx, ((vmask[i] >> skh) & (vmask[i] >> (8 + half)) & livebit) ? rowoff[i] + tapoff : -1, 0);
+                xs[i] = a3d_load4(rx, ((vmask[i] >> skh) & (vmask[i] >> (8 + half)) & livebit) ? rowoff[i] + tapoff : -1, 0);
             const int soff = kc * (BKT * 4);
             if constexpr (!WDMA) {
 #pragma unroll
-                for (int i = 0; i < WR; ++i) ws[i] = x3_load4(rw, livebit ? woff[i] : -1, soff);
+                for (int i = 0; i < WR; ++i) ws[i] = a3d_load4(rw, livebit ? woff[i] : -1, soff);
             }
             ++kc;
             return;
@@ -188,11 +159,11 @@ __global__ __launch_bounds__(256, 3) void conv_x3_kernel(const a3d_conv_desc d, 
         const __amdgpu_buffer_rsrc_t r = second ? rx2 : rx;
         const int tapoff = (kh * d.W + kw) * cs4 + (second ? c0 - d.Cin : c0) * 4;
 #pragma unroll
-        for (int i = 0; i < XR; ++i) xs[i] = x3_load4(r, ((vmask[i] >> (tap & 31)) & livebit) ? rowoff[i] + tapoff : -1, 0);
+        for (int i = 0; i < XR; ++i) xs[i] = a3d_load4(r, ((vmask[i] >> (tap & 31)) & livebit) ? rowoff[i] + tapoff : -1, 0);
         const int soff = kc * (BKT * 4);
         if constexpr (!WDMA) {
 #pragma unroll
-            for (int i = 0; i < WR; ++i) ws[i] = x3_load4(rw, livebit ? woff[i] : -1, soff);
+            for (int i = 0; i < WR; ++i) ws[i] = a3d_load4(rw, livebit ? woff[i] : -1, soff);
         }
         ++kc;
         c0 += BKT;
@@ -211,7 +182,7 @@ __global__ __launch_bounds__(256, 3) void conv_x3_kernel(const a3d_conv_desc d, 
 #pragma unroll
             for (int i = 0; i < XR; ++i) {
                 h16x4 h, l;
-                split2h(xs[i], sxr[i], h, l);
+                a3d_split2h(xs[i], sxr[i], h, l);
                 _Float16 *p = reinterpret_cast<_Float16 *>(X) + (lr + RPP * i) * LKB + lcs;
                 *reinterpret_cast<h16x4 *>(p) = h;
                 *reinterpret_cast<h16x4 *>(p + PX) = l;
@@ -220,7 +191,7 @@ __global__ __launch_bounds__(256, 3) void conv_x3_kernel(const a3d_conv_desc d, 
 #pragma unroll
                 for (int i = 0; i < WR; ++i) {
                     h16x4 h, l;
-                    split2h(ws[i], sw, h, l);
+                    a3d_split2h(ws[i], sw, h, l);
                     _Float16 *p = reinterpret_cast<_Float16 *>(Wt) + (lr + RPP * i) * LKB + lcs;
                     *reinterpret_cast<h16x4 *>(p) = h;
                     *reinterpret_cast<h16x4 *>(p + PW) = l;
@@ -231,7 +202,7 @@ __global__ __launch_bounds__(256, 3) void conv_x3_kernel(const a3d_conv_desc d, 
 #pragma unroll
         for (int i = 0; i < XR; ++i) {
             bf16x4 h, m, l;
-            split3(xs[i], h, m, l);
+            a3d_split3(xs[i], h, m, l);
             __bf16 *p = X + (lr + RPP * i) * LKB + lcs;
             *reinterpret_cast<bf16x4 *>(p) = h;
             *reinterpret_cast<bf16x4 *>(p + PX) = m;
@@ -240,7 +211,7 @@ __global__ __launch_bounds__(256, 3) void conv_x3_kernel(const a3d_conv_desc d, 
 #pragma unroll
         for (int i = 0; i < WR; ++i) {
             bf16x4 h, m, l;
-            split3(ws[i], h, m, l);
+            a3d_split3(ws[i], h, m, l);
             __bf16 *p = Wt + (lr + RPP * i) * LKB + lcs;
             *reinterpret_cast<bf16x4 *>(p) = h;
             *reinterpret_cast<bf16x4 *>(p + PW) = m;
@@ -401,14 +372,10 @@ __global__ __launch_bounds__(256, 3) void conv_x3_kernel(const a3d_conv_desc d, 
 
     const bool has_res = d.res != nullptr;
     const int hwo = d.Ho * d.Wo;
-    // Row-major epilogue.  The MFMA leaves a lane with ONE pixel and register quads of 4 channels: stored as they are, a wave
-    // instruction touches 32 rows x 32 bytes (64 separate 16-byte requests, and the same again for the residual).  Each 32 x 32 tile
-    // therefore goes through 4 KiB of LDS (quad index XOR-swizzled with the row: conflict-free both ways) and comes back with 8 lanes
-    // per row: a wave instruction then covers 8 rows x 128 contiguous bytes (res2 1x1 64 -> 256 + residual: 0.79 -> 0.61 ms).  Same
-    // values, same operations per element: the stored bits do not change.  No barrier: behind the last chunk's barrier every
-    // fragment a wave still multiplies is in registers, and the only later LDS traffic (fragment reads of a chunk that does not
-    // exist, filter DMAs past the last chunk) reads garbage nobody uses or lands in the FILTER areas -- the tiles go through the two
-    // ACTIVATION areas.  Pixel-shuffle and gated stores keep the direct form; tune 12 forces it (A/B, bit-equality test).
+    // Row-major epilogue (the tile turn of conv_prims.h).  No barrier: behind the last chunk's barrier every fragment a wave still
+    // multiplies is in registers, and the only later LDS traffic (fragment reads of a chunk that does not exist, filter DMAs past the
+    // last chunk) reads garbage nobody uses or lands in the FILTER areas -- the tiles go through the two ACTIVATION areas.
+    // Pixel-shuffle and gated stores keep the direct form; tune 12 forces it (A/B, bit-equality test).
     if (!(d.pixshuf || d.gate) && d.tune != 12) {
         static_assert(NP * PX * 2 >= 8192, "two 4 KiB tiles per activation area");
         float *T = reinterpret_cast<float *>(lds + (wave >> 1) * BUF) + (wave & 1) * 1024;
@@ -428,6 +395,7 @@ __global__ __launch_bounds__(256, 3) void conv_x3_kernel(const a3d_conv_desc d, 
                 for (int rg = 0; rg < 4; ++rg) {
                     f32x4 v = {acc[ni][mi][rg * 4 + 0], acc[ni][mi][rg * 4 + 1], acc[ni][mi][rg * 4 + 2], acc[ni][mi][rg * 4 + 3]};
                     if constexpr (F16) v = (v * unx) * unw;  // exact: powers of two
+                    // (the tile turn stays spelled out: behind a3d_turn_put / a3d_turn_get this kernel's register allocation and instruction order changed)
                     *reinterpret_cast<f32x4 *>(T + pr * 32 + (((rg * 2 + ph) ^ (pr & 7)) << 2)) = v;
                 }
                 const int nl = (wn * TN + ni) * 32 + qc * 4;
@@ -481,15 +449,11 @@ __global__ __launch_bounds__(256, 3) void conv_x3_kernel(const a3d_conv_desc d, 
                 if (mb < M && mb / hwo == mlast / hwo) {  // the tile's rows belong to one image (uniform per wave): one reduction
                     a3d_note_amax(d.y_amax, mb / hwo, fmaxf(fmaxf(vmax[0], vmax[1]), fmaxf(vmax[2], vmax[3])), true);
                 } else {
-                    // (rows of several images, e.g. the FC layers where every ROI is one: the 8 lanes of a row reduce first, so a row
-                    // costs one pre-checked atomic per wave instead of eight -- fc2 at 64000 rows 1.03 -> see DESIGN 5a)
+                    // (a3d_note_rows, spelled out: behind the helper this kernel's register allocation changed -- fc2 at 64000 rows: see DESIGN 5a)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int m = mb + qr + 8 * j;
-                        float v = vmax[j];
-                        v = fmaxf(v, __shfl_xor(v, 1, 64));
-                        v = fmaxf(v, __shfl_xor(v, 2, 64));
-                        v = fmaxf(v, __shfl_xor(v, 4, 64));
+                        const float v = a3d_max8(vmax[j]);
                         a3d_note_amax(d.y_amax, m < M ? m / hwo : 0, v, m < M && qc == 0);
                     }
                 }

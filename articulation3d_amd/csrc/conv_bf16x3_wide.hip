@@ -30,38 +30,6 @@
 #include <type_traits>
 
 namespace {
-typedef __bf16 wx_bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 wx_bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wx_rsrc(const void *p, unsigned bytes) {
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    void *q = reinterpret_cast<void *>(((unsigned long long)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(q, 0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-__device__ __forceinline__ f32x4 wx_load4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ void wx_dma16(__amdgpu_buffer_rsrc_t r, __bf16 *lds_dst, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)lds_dst, 16, voff, soff, 0, 0);
-}
-// x = h + m + l exactly (round-to-nearest-even at each level): conv_bf16x3.hip's split3
-__device__ __forceinline__ void wx_split3(const f32x4 v, wx_bf16x4 &h, wx_bf16x4 &m, wx_bf16x4 &l) {
-    h = __builtin_convertvector(v, wx_bf16x4);
-    const f32x4 r1 = v - __builtin_convertvector(h, f32x4);
-    m = __builtin_convertvector(r1, wx_bf16x4);
-    const f32x4 r2 = r1 - __builtin_convertvector(m, f32x4);
-    l = __builtin_convertvector(r2, wx_bf16x4);
-}
-
-typedef _Float16 wx_h16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 wx_h16x8 __attribute__((ext_vector_type(8)));
-// fp16x2 (precision 3): x * s = h + l, conv_bf16x3.hip's split2h
-__device__ __forceinline__ void wx_split2h(const f32x4 v, const float s, wx_h16x4 &h, wx_h16x4 &l) {
-    const f32x4 xs = v * s;
-    h = __builtin_convertvector(xs, wx_h16x4);
-    l = __builtin_convertvector(xs - __builtin_convertvector(h, f32x4), wx_h16x4);
-}
 
 constexpr int XW_BM = 256, XW_BN = 256, XW_BK = 16;
 // PH4: the phases (bit 2 dy + dx) whose 2x2 window inside the 3x3 neighbourhood holds tap kh = tap / 3, kw = tap % 3
@@ -135,10 +103,10 @@ __global__ __launch_bounds__(512, 1) void conv_x3w_kernel(const a3d_conv_desc d,
     // (XD: the pre-split tensors hold the same number of bytes per pixel as the fp32 ones: Cin / 16 chunks x 64 B)
     const void *const x0p = XD ? d.x_h2 : (const void *)d.x;
     const void *const x1p = XD ? (d.x2_h2 ? d.x2_h2 : d.x_h2) : (const void *)(d.x2 ? d.x2 : d.x);
-    const __amdgpu_buffer_rsrc_t rx = wx_rsrc(x0p, (unsigned)((size_t)d.B * d.H * d.W * (size_t)cs4));
-    const __amdgpu_buffer_rsrc_t rx2 = wx_rsrc(x1p, (unsigned)((size_t)d.B * d.H * d.W * (size_t)cs4));
+    const __amdgpu_buffer_rsrc_t rx = a3d_rsrc_uniform(x0p, (unsigned)((size_t)d.B * d.H * d.W * (size_t)cs4));
+    const __amdgpu_buffer_rsrc_t rx2 = a3d_rsrc_uniform(x1p, (unsigned)((size_t)d.B * d.H * d.W * (size_t)cs4));
     const unsigned w3chunk = (unsigned)d.Cout * 32u * NP;  // bytes of one chunk of w_x3: NP planes x Cout rows x 32 B
-    const __amdgpu_buffer_rsrc_t rw = wx_rsrc(d.w_x3, (unsigned)((size_t)nk_all * w3chunk));
+    const __amdgpu_buffer_rsrc_t rw = a3d_rsrc_uniform(d.w_x3, (unsigned)((size_t)nk_all * w3chunk));
 
     const float sw = F16 ? d.w_scale : 1.f;
     float sxr[XR];  // fp16x2: the scale of each loader row's image
@@ -175,7 +143,7 @@ __global__ __launch_bounds__(512, 1) void conv_x3w_kernel(const a3d_conv_desc d,
         const __amdgpu_buffer_rsrc_t r = second ? rx2 : rx;
         const int tapoff = (kh * d.W + kw) * cs4 + (second ? c0 - d.Cin : c0) * 4;
 #pragma unroll
-        for (int i = 0; i < XR; ++i) xs[i] = wx_load4(r, ((vmask[i] >> (tap & 31)) & livebit) ? rowoff[i] + tapoff : -1, 0);
+        for (int i = 0; i < XR; ++i) xs[i] = a3d_load4(r, ((vmask[i] >> (tap & 31)) & livebit) ? rowoff[i] + tapoff : -1, 0);
         ++kc;
         c0 += BKT;
         if (c0 >= CinT) {
@@ -187,23 +155,23 @@ __global__ __launch_bounds__(512, 1) void conv_x3w_kernel(const a3d_conv_desc d,
         }
     };
     struct Split {
-        wx_bf16x4 h, m, l;  // (fp16x2: h, m hold the two fp16 planes' bits)
+        bf16x4 h, m, l;  // (fp16x2: h, m hold the two fp16 planes' bits)
     };
     auto split = [&](const f32x4 v, const int i, Split &o) {
         if constexpr (F16) {
-            wx_h16x4 h, l;
-            wx_split2h(v, sxr[i], h, l);
-            o.h = __builtin_bit_cast(wx_bf16x4, h);
-            o.m = __builtin_bit_cast(wx_bf16x4, l);
+            h16x4 h, l;
+            a3d_split2h(v, sxr[i], h, l);
+            o.h = __builtin_bit_cast(bf16x4, h);
+            o.m = __builtin_bit_cast(bf16x4, l);
         } else {
-            wx_split3(v, o.h, o.m, o.l);
+            a3d_split3(v, o.h, o.m, o.l);
         }
     };
     auto put = [&](const int xst, const int i, const Split &v) {  // the planes of loader row lr + RPP i
         __bf16 *p = Xs + xst * XW_XST + (lr + RPP * i) * LKB + lcs;
-        *reinterpret_cast<wx_bf16x4 *>(p) = v.h;
-        *reinterpret_cast<wx_bf16x4 *>(p + PX) = v.m;
-        if constexpr (!F16) *reinterpret_cast<wx_bf16x4 *>(p + 2 * PX) = v.l;
+        *reinterpret_cast<bf16x4 *>(p) = v.h;
+        *reinterpret_cast<bf16x4 *>(p + PX) = v.m;
+        if constexpr (!F16) *reinterpret_cast<bf16x4 *>(p + 2 * PX) = v.l;
     };
     // weights: w_x3 [Kpad/16][3][Cout][16] bf16; one (chunk, plane) tile of this workgroup's 256 rows is an 8 KiB run = 8 DMA
     // wave-instructions of 32 rows.  Lane i of an instruction lands at LDS byte 16 i of its 1 KiB = row i/2, half i%2, and fetches
@@ -219,7 +187,7 @@ __global__ __launch_bounds__(512, 1) void conv_x3w_kernel(const a3d_conv_desc d,
         for (int i = 0; i < NP; ++i) {
             const int j = wave * NP + i;  // 8 NP instructions per chunk: plane j/8, row group j%8
             const int p = j >> 3, g = j & 7;
-            wx_dma16(rw, Wt + p * PW + g * 32 * LKB, wvoff, base + __builtin_amdgcn_readfirstlane(p * d.Cout * 32 + g * 1024));
+            a3d_dma16(rw, Wt + p * PW + g * 32 * LKB, wvoff, base + __builtin_amdgcn_readfirstlane(p * d.Cout * 32 + g * 1024));
         }
         ++dma_c;
         dma_st = dma_st == NWS - 1 ? 0 : dma_st + 1;
@@ -260,7 +228,7 @@ __global__ __launch_bounds__(512, 1) void conv_x3w_kernel(const a3d_conv_desc d,
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int g = (wave * 2 + i) & 7;
-            wx_dma16(r, Xt + g * 32 * LKB, ((xd_mask[i] >> (tap & 31)) & livebit) ? xd_off[i] + tapoff : -1, p * 32);
+            a3d_dma16(r, Xt + g * 32 * LKB, ((xd_mask[i] >> (tap & 31)) & livebit) ? xd_off[i] + tapoff : -1, p * 32);
         }
         ++kc;
         c0 += BKT;
@@ -289,23 +257,23 @@ __global__ __launch_bounds__(512, 1) void conv_x3w_kernel(const a3d_conv_desc d,
     const __bf16 *const fX = Xs + (wm * TM * 32) * LKB + frag_off;
     const __bf16 *const fW = Ws + (wn * TN * 32) * LKB + frag_off;
     struct FragA {
-        wx_bf16x8 p[NP];  // weights of one 32-channel block, hi | mid | lo
+        bf16x8 p[NP];  // weights of one 32-channel block, hi | mid | lo
     };
     struct FragB {
-        wx_bf16x8 p[NP][TM];  // activations of the wave's two 32-pixel blocks
+        bf16x8 p[NP][TM];  // activations of the wave's two 32-pixel blocks
     };
     auto rdA = [&](FragA &A, const int wst, const int n) {
 #pragma unroll
-        for (int p = 0; p < NP; ++p) A.p[p] = *reinterpret_cast<const wx_bf16x8 *>(fW + wst * XW_WST + p * PW + n * 32 * LKB);
+        for (int p = 0; p < NP; ++p) A.p[p] = *reinterpret_cast<const bf16x8 *>(fW + wst * XW_WST + p * PW + n * 32 * LKB);
     };
     auto rdB = [&](FragB &Bf, const int xst, const int p) {
 #pragma unroll
-        for (int mi = 0; mi < TM; ++mi) Bf.p[p][mi] = *reinterpret_cast<const wx_bf16x8 *>(fX + xst * XW_XST + p * PX + mi * 32 * LKB);
+        for (int mi = 0; mi < TM; ++mi) Bf.p[p][mi] = *reinterpret_cast<const bf16x8 *>(fX + xst * XW_XST + p * PX + mi * 32 * LKB);
     };
 
 #define XW_FENCE __builtin_amdgcn_sched_barrier(0);
 #define XW_MFMA(C, A, Bv)                                                                                                              \
-    if constexpr (F16) C = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wx_h16x8, A), __builtin_bit_cast(wx_h16x8, Bv), C, 0, 0, 0); \
+    if constexpr (F16) C = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, A), __builtin_bit_cast(h16x8, Bv), C, 0, 0, 0); \
     else C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, Bv, C, 0, 0, 0);
 #define XW_TERM(N, A, Bf, PA, PB)                \
     XW_MFMA(acc[N][0], A.p[PA], Bf.p[PB][0]) \
@@ -472,7 +440,7 @@ __global__ __launch_bounds__(512, 1) void conv_x3w_kernel(const a3d_conv_desc d,
             dma_x();
             dma_w();
         }
-        __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"((XD_NST - 1) * OPS) : "memory");
+        a3d_wait_vm<(XD_NST - 1) * OPS>();
         __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (scale / shift staged above)
         __builtin_amdgcn_s_barrier();
         rdB(B0, 0, 0);
@@ -502,7 +470,7 @@ __global__ __launch_bounds__(512, 1) void conv_x3w_kernel(const a3d_conv_desc d,
             XW_TERM(2, A0, Bc, 0, 1)
             XW_TERM(2, A0, Bc, 1, 0)
             XW_FENCE
-            __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"((XD_NST - 2) * OPS) : "memory");
+            a3d_wait_vm<(XD_NST - 2) * OPS>();
             __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #ifdef A3D_ABLATIONS  // timing-only variants (developer builds, A3D_HIPCC_FLAGS=-DA3D_ABLATIONS): tune bit 10 no activation DMA, 11 no filter DMA, 12 no barrier
             if (!(d.tune & 4096)) __builtin_amdgcn_s_barrier();

@@ -19,13 +19,8 @@
 #include "conv_common.h"
 
 namespace {
-typedef __bf16 bx_bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bx_bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int bx_u32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t bx_rsrc(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
 __device__ __forceinline__ f32x4 bx_widen4(const bx_u32x2 v) {
     f32x4 o;
     o[0] = __builtin_bit_cast(float, v[0] << 16);
@@ -33,10 +28,6 @@ __device__ __forceinline__ f32x4 bx_widen4(const bx_u32x2 v) {
     o[2] = __builtin_bit_cast(float, v[1] << 16);
     o[3] = __builtin_bit_cast(float, v[1] & 0xFFFF0000u);
     return o;
-}
-template <int N>
-__device__ __forceinline__ void bx_wait_vm() {
-    __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 constexpr int BX_NST = 7;         // ring stages of 8 KiB
@@ -76,7 +67,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16xs_kernel(const a3d_conv_desc
     // wave-instruction lands at LDS byte 16 i of the piece = row i / 2, half i % 2, and fetches the k half the image keeps there:
     // half ^ ((row >> 3) & 1) (the fragment reads below are then conflict-free).  A stage holds pieces [chunk-in-stage][group];
     // wave w moves pieces 2w and 2w + 1.
-    const __amdgpu_buffer_rsrc_t rw = bx_rsrc(d.w_bf16, (unsigned)((size_t)d.Cout * d.Kpad * 2));
+    const __amdgpu_buffer_rsrc_t rw = a3d_rsrc(d.w_bf16, (unsigned)((size_t)d.Cout * d.Kpad * 2));
     const int wvoff = ((lane >> 1) * d.Kpad + (((lane & 1) ^ ((lane >> 4) & 1)) << 3)) * 2;
     const int uw = __builtin_amdgcn_readfirstlane(wave);
     int dma_q = 0, dma_st = 0, rd_st = 0;  // next step to fetch; ring stage it goes to; ring stage the next fragment reads come from
@@ -92,8 +83,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16xs_kernel(const a3d_conv_desc
             const int kl = j / NG, g = j % NG;
             const int c = t * KS + kl;
             const int soff = q < Q ? ((nbeg + ns * BN + g * 32) * d.Kpad + c * 16) * 2 : 0;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void *)(st + j * 1024), 16, voff,
-                                                     __builtin_amdgcn_readfirstlane(soff), 0, 0);
+            a3d_dma16(rw, st + j * 1024, voff, __builtin_amdgcn_readfirstlane(soff));
         }
     };
 #pragma unroll
@@ -102,15 +92,15 @@ __global__ __launch_bounds__(256, 2) void conv_bf16xs_kernel(const a3d_conv_desc
     // ---- the wave's activations: lane (pixel lane % 32, k group lane / 32) holds channels 16 c + 8 (lane / 32) .. + 7 of every chunk c
     const int mp = m0 + (lane & 31);
     const bool mok = mp < M;
-    bx_bf16x8 xb[KC];
+    bf16x8 xb[KC];
     {
         constexpr int XES = XB ? 2 : 4;
-        const __amdgpu_buffer_rsrc_t rx = bx_rsrc(d.x, (unsigned)((size_t)M * d.Cin * XES));
+        const __amdgpu_buffer_rsrc_t rx = a3d_rsrc(d.x, (unsigned)((size_t)M * d.Cin * XES));
         const int voff = mok ? (mp * d.Cin + (lane >> 5) * 8) * XES : -1;
         if constexpr (XB) {
 #pragma unroll
-            for (int c = 0; c < KC; ++c) xb[c] = __builtin_bit_cast(bx_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rx, voff, c * 32, 0));
-            bx_wait_vm<0>();
+            for (int c = 0; c < KC; ++c) xb[c] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rx, voff, c * 32, 0));
+            a3d_wait_vm<0>();
         } else {
             constexpr int CB = KC < 8 ? KC : 8;  // chunks per batch of fp32 loads (64 transient registers)
 #pragma unroll
@@ -118,13 +108,13 @@ __global__ __launch_bounds__(256, 2) void conv_bf16xs_kernel(const a3d_conv_desc
                 f32x4 raw[CB][2];
 #pragma unroll
                 for (int c = 0; c < CB; ++c) {
-                    raw[c][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, voff, (c0 + c) * 64, 0));
-                    raw[c][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, voff, (c0 + c) * 64 + 16, 0));
+                    raw[c][0] = a3d_load4(rx, voff, (c0 + c) * 64);
+                    raw[c][1] = a3d_load4(rx, voff, (c0 + c) * 64 + 16);
                 }
-                bx_wait_vm<0>();
+                a3d_wait_vm<0>();
 #pragma unroll
                 for (int c = 0; c < CB; ++c) {
-                    const bx_bf16x4 lo = __builtin_convertvector(raw[c][0], bx_bf16x4), hi = __builtin_convertvector(raw[c][1], bx_bf16x4);
+                    const bf16x4 lo = __builtin_convertvector(raw[c][0], bf16x4), hi = __builtin_convertvector(raw[c][1], bf16x4);
                     xb[c0 + c] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
                 }
             }
@@ -140,8 +130,8 @@ __global__ __launch_bounds__(256, 2) void conv_bf16xs_kernel(const a3d_conv_desc
     const bool yb = d.io_bf16 & 2;
     const bool side = has_res || has_gate;
     const unsigned obytes = (unsigned)((size_t)M * d.Cout * 2);
-    const __amdgpu_buffer_rsrc_t rres = bx_rsrc(has_res ? (const void *)d.res : (const void *)d.w_bf16, has_res ? obytes : 0u);
-    const __amdgpu_buffer_rsrc_t rgate = bx_rsrc(has_gate ? (const void *)d.gate : (const void *)d.w_bf16, has_gate ? obytes : 0u);
+    const __amdgpu_buffer_rsrc_t rres = a3d_rsrc(has_res ? (const void *)d.res : (const void *)d.w_bf16, has_res ? obytes : 0u);
+    const __amdgpu_buffer_rsrc_t rgate = a3d_rsrc(has_gate ? (const void *)d.gate : (const void *)d.w_bf16, has_gate ? obytes : 0u);
 
     for (int ns = 0, q = 0; ns < nsteps; ++ns) {
         const int n0 = nbeg + ns * BN;
@@ -176,8 +166,8 @@ __global__ __launch_bounds__(256, 2) void conv_bf16xs_kernel(const a3d_conv_desc
         for (int t = 0; t < SPT; ++t, ++q) {
             // the DMA of step q (issued BX_D steps ago) has landed: younger than it are the DMAs of the BX_D - 1 steps since and, during
             // the first BX_D steps of an N step, that step's residual / gate loads (loads retire in order; stores only make the wait stricter)
-            if (side && t < BX_D) bx_wait_vm<2 * (BX_D - 1) + R>();
-            else bx_wait_vm<2 * (BX_D - 1)>();
+            if (side && t < BX_D) a3d_wait_vm<2 * (BX_D - 1) + R>();
+            else a3d_wait_vm<2 * (BX_D - 1)>();
             // (a bare barrier: __syncthreads() carries a workgroup fence, and the compiler completes every LDS-DMA in flight in front of it)
             __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
@@ -187,23 +177,24 @@ __global__ __launch_bounds__(256, 2) void conv_bf16xs_kernel(const a3d_conv_desc
 #pragma unroll
             for (int kl = 0; kl < KS; ++kl) {
                 const int c = t * KS + kl;
-                bx_bf16x8 fa[NG];
+                bf16x8 fa[NG];
 #pragma unroll
-                for (int g = 0; g < NG; ++g) fa[g] = *reinterpret_cast<const bx_bf16x8 *>(st + (kl * NG + g) * 1024);
+                for (int g = 0; g < NG; ++g) fa[g] = *reinterpret_cast<const bf16x8 *>(st + (kl * NG + g) * 1024);
 #pragma unroll
                 for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[g], xb[c], acc[g], 0, 0, 0);
             }
         }
         // ---- epilogue of the N step: a 32 x 32 tile goes through 4 KiB of LDS (XOR-swizzled) and comes back row-major
         if (side) {  // the residual / gate loads are older than the DMAs of the last min(SPT, BX_D) steps
-            if constexpr (SPT < BX_D) bx_wait_vm<2 * SPT>();
-            else bx_wait_vm<2 * BX_D>();
+            if constexpr (SPT < BX_D) a3d_wait_vm<2 * SPT>();
+            else a3d_wait_vm<2 * BX_D>();
         }
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
 #pragma unroll
             for (int rg = 0; rg < 4; ++rg) {
                 const f32x4 v = {acc[g][rg * 4 + 0], acc[g][rg * 4 + 1], acc[g][rg * 4 + 2], acc[g][rg * 4 + 3]};
+                // (the tile turn stays spelled out: behind a3d_turn_put / a3d_turn_get this kernel's register allocation and instruction order changed)
                 *reinterpret_cast<f32x4 *>(T + pr * 32 + (((rg * 2 + ph) ^ (pr & 7)) << 2)) = v;
             }
             const int nl = g * 32 + qc * 4;
@@ -225,12 +216,12 @@ __global__ __launch_bounds__(256, 2) void conv_bf16xs_kernel(const a3d_conv_desc
                     for (int i = 0; i < 4; ++i) v[i] = gq[i] > 0.f ? v[i] : 0.f;
                 }
                 const size_t o = (size_t)m * d.Cout + n0 + nl;
-                if (yb) *reinterpret_cast<bx_bf16x4 *>(reinterpret_cast<__bf16 *>(d.y) + o) = __builtin_convertvector(v, bx_bf16x4);
+                if (yb) *reinterpret_cast<bf16x4 *>(reinterpret_cast<__bf16 *>(d.y) + o) = __builtin_convertvector(v, bf16x4);
                 else *reinterpret_cast<f32x4 *>(d.y + o) = v;
             }
         }
     }
-    bx_wait_vm<0>();  // the DMAs issued past the last step must not land in the LDS of the next workgroup
+    a3d_wait_vm<0>();  // the DMAs issued past the last step must not land in the LDS of the next workgroup
 }
 
 template <int KC, int NG, int KS>

@@ -1,6 +1,6 @@
 // Shared pieces of the conv-GEMM kernels: tile constants and the fused epilogue.
 #pragma once
-#include "a3d_common.h"
+#include "conv_prims.h"
 #include "../../include/a3d.h"
 
 #define BK 32
@@ -13,25 +13,8 @@ __device__ __forceinline__ float a3d_act(float v) {
     return v;
 }
 
-__device__ __forceinline__ f32x4 apply_epilogue(const a3d_conv_desc &d, f32x4 v, int n, size_t res_row) {
-    f32x4 s = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
-    if (d.scale) s = *reinterpret_cast<const f32x4 *>(d.scale + n);
-    if (d.shift) sh = *reinterpret_cast<const f32x4 *>(d.shift + n);
-    for (int i = 0; i < 4; ++i) v[i] = __builtin_fmaf(v[i], s[i], sh[i]);  // same rounding as a3d_epilogue_math below
-    if (d.res) {
-        const f32x4 r = *reinterpret_cast<const f32x4 *>(d.res + res_row * (size_t)d.Cout + n);
-        v += r;
-    }
-    if (d.act == A3D_ACT_RELU) {
-        for (int i = 0; i < 4; ++i) v[i] = v[i] <= 0.f ? 0.f : v[i];
-    } else if (d.act == A3D_ACT_LEAKY) {
-        for (int i = 0; i < 4; ++i) v[i] = v[i] > 0.f ? v[i] : 0.01f * v[i];
-    }
-    return v;
-}
-
 // ---- fast epilogue ---------------------------------------------------------------------------------------------
-// The per-quad form above issues three dependent global loads (scale, shift, residual) per output quad, and because
+// A per-quad form issues three dependent global loads (scale, shift, residual) per output quad, and because
 // y / res / gate may alias the compiler keeps every one of them in program order with the stores: 16 serialized
 // round trips per wave.  The kernels therefore stage scale / shift of their N tile in LDS once (a3d_stage_scale_shift)
 // and fetch all residual quads of an output row before its first store (one wait instead of eight).
@@ -106,22 +89,6 @@ __device__ __forceinline__ float a3d_in_scale(const a3d_conv_desc &d, const int 
     float a = d.in_amax[b];
     if (d.in_amax2) a = fmaxf(a, d.in_amax2[b]);
     return a3d_pow2_scale(a);
-}
-// y_amax[b] = max(y_amax[b], v) for the lanes with `valid`; v >= 0.  One atomic per wave when the wave's valid lanes share b (the
-// rule: 32 consecutive pixels of one image), and none at all once the slot already holds a larger value.
-__device__ __forceinline__ void a3d_note_amax(float *y_amax, const int b, float v, const bool valid) {
-    if (!valid) v = 0.f;
-    const unsigned long long live = __ballot(valid);
-    if (!live) return;
-    const int b0 = __shfl(b, __ffsll((long long)live) - 1, 64);
-    const bool uniform = __all(!valid || b == b0);
-    if (uniform) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-        if ((threadIdx.x & 63) == 0 && v > y_amax[b0]) atomicMax(reinterpret_cast<int *>(y_amax + b0), __float_as_int(v));
-    } else if (valid && v > y_amax[b]) {
-        atomicMax(reinterpret_cast<int *>(y_amax + b), __float_as_int(v));
-    }
 }
 // Every conv launcher records the kernel instantiation it dispatched (name + template arguments as they appear in a
 // rocprofv3 kernel trace) in a per-thread slot; `a3d_last_conv_variant()` (include/a3d.h) reads it back, so measurement

@@ -16,14 +16,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 enum { MODE_GENERIC = 0, MODE_UPS = 1, MODE_STEM = 2 };
 
-__device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
-
 // uniform (scalar) position of the current k-chunk inside the filter
 struct ChunkPos {
     int kc;       // chunk index (k = 32*kc)
@@ -64,9 +56,9 @@ __global__ __launch_bounds__(WAVES_M *WAVES_N * 64, (BKT == 16 && PIPE == 0) ? 3
     const int CinT = (MODE == MODE_STEM) ? 32 : d.Cin + d.Cin2;
     const int cs4 = (MODE == MODE_STEM) ? 16 : d.Cin * 4;  // bytes between consecutive pixels of a source
     const unsigned xbytes = (unsigned)((size_t)d.B * d.H * d.W * (size_t)cs4);
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(d.x, xbytes);
-    const __amdgpu_buffer_rsrc_t rx2 = make_rsrc(d.x2 ? d.x2 : d.x, xbytes);
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(d.w, (unsigned)((size_t)d.Cout * d.Kpad * 4));
+    const __amdgpu_buffer_rsrc_t rx = a3d_rsrc(d.x, xbytes);
+    const __amdgpu_buffer_rsrc_t rx2 = a3d_rsrc(d.x2 ? d.x2 : d.x, xbytes);
+    const __amdgpu_buffer_rsrc_t rw = a3d_rsrc(d.w, (unsigned)((size_t)d.Cout * d.Kpad * 4));
 
     // ---- per-row loop invariants ---------------------------------------------------------------
     int rowoff[XR];      // GENERIC/STEM: byte offset of (b, ih0, iw0[+j], lc) -- may be "negative", used mod 2^32
@@ -160,7 +152,7 @@ __global__ __launch_bounds__(WAVES_M *WAVES_N * 64, (BKT == 16 && PIPE == 0) ? 3
                 const int ih = (uih0[i] + pos.kh) >> 1, iw = (uiw0[i] + pos.kw) >> 1;
                 const int off = (uboff[i] + ih * d.W + iw) * cs4 + ccb;
                 const bool ok = ((vmask[i] >> (tap & 31)) & livebit) != 0;
-                xs[i] = buf_load4(r, ok ? off : -1, 0);
+                xs[i] = a3d_load4(r, ok ? off : -1, 0);
             }
         } else {
             const int tapoff = (MODE == MODE_STEM) ? pos.kh * d.W * 16
@@ -168,12 +160,12 @@ __global__ __launch_bounds__(WAVES_M *WAVES_N * 64, (BKT == 16 && PIPE == 0) ? 3
 #pragma unroll
             for (int i = 0; i < XR; ++i) {
                 const bool ok = ((vmask[i] >> (tap & 31)) & livebit) != 0;
-                xs[i] = buf_load4(r, ok ? rowoff[i] + tapoff : -1, 0);
+                xs[i] = a3d_load4(r, ok ? rowoff[i] + tapoff : -1, 0);
             }
         }
         const int soff = pos.kc * (BKT * 4);
 #pragma unroll
-        for (int i = 0; i < WR; ++i) ws[i] = buf_load4(rw, live ? woff[i] : -1, soff);
+        for (int i = 0; i < WR; ++i) ws[i] = a3d_load4(rw, live ? woff[i] : -1, soff);
         advance();
     };
     auto store_chunk = [&](int buf, const f32x4 (&xs)[XR], const f32x4 (&ws)[WR]) {
@@ -323,7 +315,11 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_v2_kernel(const a3d_co
         size_t res_row;
         int b, oh, ow;
         out_rows(d, m, res_row, b, oh, ow);
-        v = apply_epilogue(d, v, n, res_row);
+        f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f}, r = sh;
+        if (d.scale) sc = *reinterpret_cast<const f32x4 *>(d.scale + n);
+        if (d.shift) sh = *reinterpret_cast<const f32x4 *>(d.shift + n);
+        if (d.res) r = *reinterpret_cast<const f32x4 *>(d.res + res_row * (size_t)d.Cout + n);
+        v = a3d_epilogue_math(d, v, sc, sh, d.res != nullptr, r);
         store_out(d, v, m, n, b, oh, ow);
         if (d.y_amax) amax_v = a3d_absmax4(v), amax_b = m / (d.Ho * d.Wo);
         }

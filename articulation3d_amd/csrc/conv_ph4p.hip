@@ -23,23 +23,6 @@
 #include <type_traits>
 
 namespace {
-typedef __bf16 pp_bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 pp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 pp_h16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 pp_h16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t pp_rsrc(const void *p, unsigned bytes) {
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    void *q = reinterpret_cast<void *>(((unsigned long long)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(q, 0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-__device__ __forceinline__ f32x4 pp_load4(__amdgpu_buffer_rsrc_t r, int voff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
-}
-__device__ __forceinline__ void pp_dma16(__amdgpu_buffer_rsrc_t r, __bf16 *lds_dst, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)lds_dst, 16, voff, soff, 0, 0);
-}
 
 // Tile shapes: 8 x 32 (a 32-pixel MFMA block = one tile row: its fragment rows are 32 consecutive patch positions at every tap, the
 // conflict-free case) or 16 x 16 (a block = two tile rows: 2-way bank conflicts on some taps' activation reads, but 64 x 80 instead of
@@ -103,10 +86,10 @@ __global__ __launch_bounds__(512, NB == 1 ? 2 : 1) void conv_ph4p_kernel(const a
     const int ty0 = (tr / tiles_x) * PP_TH, tx0 = (tr % tiles_x) * PP_TW;
     const int n0 = nt * BN;
     const int CinT = d.Cin + d.Cin2, cs4 = d.Cin * 4, nchunks = CinT >> 4;
-    const __amdgpu_buffer_rsrc_t rx = pp_rsrc(d.x, (unsigned)((size_t)d.B * d.H * d.W * (size_t)cs4));
-    const __amdgpu_buffer_rsrc_t rx2 = pp_rsrc(d.x2 ? d.x2 : d.x, (unsigned)((size_t)d.B * d.H * d.W * (size_t)cs4));
+    const __amdgpu_buffer_rsrc_t rx = a3d_rsrc_uniform(d.x, (unsigned)((size_t)d.B * d.H * d.W * (size_t)cs4));
+    const __amdgpu_buffer_rsrc_t rx2 = a3d_rsrc_uniform(d.x2 ? d.x2 : d.x, (unsigned)((size_t)d.B * d.H * d.W * (size_t)cs4));
     const unsigned w3chunk = (unsigned)d.Cout * 64u;  // bytes of one 16-deep chunk of w_x3: 2 planes x Cout rows x 32 B
-    const __amdgpu_buffer_rsrc_t rw = pp_rsrc(d.w_x3, (unsigned)((size_t)(d.Kpad >> 4) * w3chunk));
+    const __amdgpu_buffer_rsrc_t rw = a3d_rsrc_uniform(d.w_x3, (unsigned)((size_t)(d.Kpad >> 4) * w3chunk));
     const float sx = a3d_in_scale(d, b), sw = d.w_scale;
 
     // ---- patch loader: item j = (position j / 4, channel quad j % 4) of the 16-channel chunk; pixels outside the image read zeros
@@ -130,18 +113,17 @@ __global__ __launch_bounds__(512, NB == 1 ? 2 : 1) void conv_ph4p_kernel(const a
         const __amdgpu_buffer_rsrc_t r = second ? rx2 : rx;
         const int coff = __builtin_amdgcn_readfirstlane((second ? c0 - d.Cin : c0) * 4);
 #pragma unroll
-        for (int i = 0; i < PP_LI; ++i) xs[i] = pp_load4(r, (live && ((inmask >> i) & 1u)) ? pixoff[i] + coff : -1);
+        for (int i = 0; i < PP_LI; ++i) xs[i] = a3d_load4(r, (live && ((inmask >> i) & 1u)) ? pixoff[i] + coff : -1, 0);
     };
     auto store_patch = [&](const int buf) {
 #pragma unroll
         for (int i = 0; i < PP_LI; ++i) {
             if (ldsoff[i] < 0) continue;
-            const f32x4 v = xs[i] * sx;
-            const pp_h16x4 h = __builtin_convertvector(v, pp_h16x4);
-            const pp_h16x4 l = __builtin_convertvector(v - __builtin_convertvector(h, f32x4), pp_h16x4);
+            h16x4 h, l;
+            a3d_split2h(xs[i], sx, h, l);
             __bf16 *p = Xs + buf * PP_XBUF + ldsoff[i];
-            *reinterpret_cast<pp_h16x4 *>(p) = h;
-            *reinterpret_cast<pp_h16x4 *>(p + PP_XPL) = l;
+            *reinterpret_cast<h16x4 *>(p) = h;
+            *reinterpret_cast<h16x4 *>(p + PP_XPL) = l;
         }
     };
     // ---- filter ring: w_x3 [Kpad / 16][h | l][Cout][16], k = (tap, c): chunk index tap * nchunks + c.  One (chunk, plane) tile of the
@@ -159,7 +141,7 @@ __global__ __launch_bounds__(512, NB == 1 ? 2 : 1) void conv_ph4p_kernel(const a
                 const int j = wave + 8 * i;
                 const int p = j / (BN / 32), gg = j % (BN / 32);
                 if (j < 2 * (BN / 32))  // (narrow tiles: fewer pieces than waves; a wave without one waits conservatively)
-                    pp_dma16(rw, Wt + p * PP_WPL + gg * 32 * 16, wvoff, base + __builtin_amdgcn_readfirstlane(p * d.Cout * 32 + gg * 1024));
+                    a3d_dma16(rw, Wt + p * PP_WPL + gg * 32 * 16, wvoff, base + __builtin_amdgcn_readfirstlane(p * d.Cout * 32 + gg * 1024));
             }
         }
     };
@@ -181,25 +163,25 @@ __global__ __launch_bounds__(512, NB == 1 ? 2 : 1) void conv_ph4p_kernel(const a
     constexpr int RPB = TW == 32 ? 1 : 2;  // tile rows per block
     const int posb0 = (2 * RPB * wm + prow) * PP_PC + pcol, posb1 = posb0 + RPB * PP_PC;
     struct FragA {
-        pp_bf16x8 p[2];
+        bf16x8 p[2];
     };
     struct FragB {
-        pp_bf16x8 p[2][2];  // [plane][tile row of the wave]
+        bf16x8 p[2][2];  // [plane][tile row of the wave]
     };
     auto rdA = [&](FragA &A, const int stage, const int n) {
 #pragma unroll
-        for (int p = 0; p < 2; ++p) A.p[p] = *reinterpret_cast<const pp_bf16x8 *>(fW + stage * PP_WST + p * PP_WPL + n * 32 * 16);
+        for (int p = 0; p < 2; ++p) A.p[p] = *reinterpret_cast<const bf16x8 *>(fW + stage * PP_WST + p * PP_WPL + n * 32 * 16);
     };
     auto rdB = [&](FragB &Bf, const int buf, const int toff) {
         const int p0 = posb0 + toff, p1 = posb1 + toff;
         const int o0 = p0 * 16 + (((khalf ^ (p0 >> 3)) & 1) << 3), o1 = p1 * 16 + (((khalf ^ (p1 >> 3)) & 1) << 3);
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-            Bf.p[p][0] = *reinterpret_cast<const pp_bf16x8 *>(Xs + buf * PP_XBUF + p * PP_XPL + o0);
-            Bf.p[p][1] = *reinterpret_cast<const pp_bf16x8 *>(Xs + buf * PP_XBUF + p * PP_XPL + o1);
+            Bf.p[p][0] = *reinterpret_cast<const bf16x8 *>(Xs + buf * PP_XBUF + p * PP_XPL + o0);
+            Bf.p[p][1] = *reinterpret_cast<const bf16x8 *>(Xs + buf * PP_XBUF + p * PP_XPL + o1);
         }
     };
-#define PP_MFMA(C, A, Bv) C = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(pp_h16x8, A), __builtin_bit_cast(pp_h16x8, Bv), C, 0, 0, 0);
+#define PP_MFMA(C, A, Bv) C = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, A), __builtin_bit_cast(h16x8, Bv), C, 0, 0, 0);
 #define PP_BLOCK(N, A, Bf)                   \
     PP_MFMA(acc[N][0], A.p[0], Bf.p[0][0]) \
     PP_MFMA(acc[N][1], A.p[0], Bf.p[0][1]) \
@@ -276,7 +258,7 @@ __global__ __launch_bounds__(512, NB == 1 ? 2 : 1) void conv_ph4p_kernel(const a
         tap(PP_T(0), TF{}, E{}, h0 * 3 + 0, buf, h0 * 3 + 1);
         tap(PP_T(1), TF{}, O{}, h0 * 3 + 1, buf, h0 * 3 + 2);
         tap(PP_T(2), TT{}, E{}, h0 * 3 + 2, buf, 0);
-        __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"(PP_LI) : "memory");  // filter group 1 has landed (younger: the patch loads)
+        a3d_wait_vm<PP_LI>();  // filter group 1 has landed (younger: the patch loads)
         __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         // ---- group 1: taps 3, 4, 5 (two, four, two)

@@ -20,12 +20,6 @@
 #include "conv_common.h"
 
 namespace {
-__device__ __forceinline__ f32x4 pw_load4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t pw_rsrc(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
 
 template <int TM, int TN, int BKT>
 __global__ __launch_bounds__(256, 3) void conv_pw_kernel(const a3d_conv_desc d, const int M, const int ntiles, const int total_tiles) {
@@ -42,8 +36,8 @@ __global__ __launch_bounds__(256, 3) void conv_pw_kernel(const a3d_conv_desc d, 
     const int lr = tid / TPR, lc = (tid % TPR) * 4;
     const int K = d.Kpad;  // == Cin for the layers routed here
     const int nk = K / BKT;
-    const __amdgpu_buffer_rsrc_t rx = pw_rsrc(d.x, (unsigned)((size_t)M * K * 4));
-    const __amdgpu_buffer_rsrc_t rw = pw_rsrc(d.w, (unsigned)((size_t)d.Cout * K * 4));
+    const __amdgpu_buffer_rsrc_t rx = a3d_rsrc(d.x, (unsigned)((size_t)M * K * 4));
+    const __amdgpu_buffer_rsrc_t rw = a3d_rsrc(d.w, (unsigned)((size_t)d.Cout * K * 4));
     int xbase[XR], wbase[WR];
 #pragma unroll
     for (int i = 0; i < XR; ++i) xbase[i] = ((lr + RPP * i) * K + lc) * 4;
@@ -58,9 +52,9 @@ __global__ __launch_bounds__(256, 3) void conv_pw_kernel(const a3d_conv_desc d, 
         const int soff = ld_k * (BKT * 4);
         // tiles past the end have m0 >= M: the range check returns zeros, no branch needed
 #pragma unroll
-        for (int i = 0; i < XR; ++i) xs[i] = pw_load4(rx, xbase[i] + ld_xrow, soff);
+        for (int i = 0; i < XR; ++i) xs[i] = a3d_load4(rx, xbase[i] + ld_xrow, soff);
 #pragma unroll
-        for (int i = 0; i < WR; ++i) ws[i] = pw_load4(rw, wbase[i] + ld_wrow, soff);
+        for (int i = 0; i < WR; ++i) ws[i] = a3d_load4(rw, wbase[i] + ld_wrow, soff);
         if (++ld_k == nk) {
             ld_k = 0;
             ld_tile += gridDim.x;

@@ -22,19 +22,6 @@
 #include "conv_common.h"
 
 namespace {
-typedef _Float16 sg_h16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 sg_h16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t sg_rsrc(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
-// x * s = h + l (conv_bf16x3.hip split2h, element for element)
-__device__ __forceinline__ void sg_split(const f32x4 v, const float s, sg_h16x4 &h, sg_h16x4 &l) {
-    const f32x4 xs = v * s;
-    h = __builtin_convertvector(xs, sg_h16x4);
-    const f32x4 r = xs - __builtin_convertvector(h, f32x4);
-    l = __builtin_convertvector(r, sg_h16x4);
-}
 
 // R = chunks of 16 input channels in flight per wave (Cin / 16 is a multiple of R).
 template <int R>
@@ -52,30 +39,30 @@ __global__ __launch_bounds__(64) void conv_sg_kernel(const a3d_conv_desc d, cons
     const float sx = mok ? a3d_in_scale(d, b) : 1.f;
     const int nk = d.Cin >> 4;
 
-    const __amdgpu_buffer_rsrc_t rx = sg_rsrc(d.x, (unsigned)((size_t)d.B * d.H * d.W * d.Cin * 4));
-    const __amdgpu_buffer_rsrc_t rw = sg_rsrc(d.w_x3, (unsigned)((size_t)nk * d.Cout * 64));
+    const __amdgpu_buffer_rsrc_t rx = a3d_rsrc(d.x, (unsigned)((size_t)d.B * d.H * d.W * d.Cin * 4));
+    const __amdgpu_buffer_rsrc_t rw = a3d_rsrc(d.w_x3, (unsigned)((size_t)nk * d.Cout * 64));
     const int xoff = mok ? (((b * d.H + oh * d.stride) * d.W + ow * d.stride) * d.Cin + ph * 8) * 4 : -1;  // (rows past M read as zeros)
     const int woff = (n0 + pr) * 32 + ph * 16;  // w_x3 [Cin/16][2][Cout][16] fp16: row n of (chunk, plane) is 32 contiguous bytes
     const int wplane = d.Cout * 32;
 
     f32x4 xa[R][2];
-    sg_h16x8 wf[R][2];
+    h16x8 wf[R][2];
     auto issue = [&](const int slot, const int c) {
-        xa[slot][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, xoff, c * 64, 0));
-        xa[slot][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, xoff, c * 64 + 16, 0));
-        wf[slot][0] = __builtin_bit_cast(sg_h16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, woff, (2 * c) * wplane, 0));
-        wf[slot][1] = __builtin_bit_cast(sg_h16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, woff, (2 * c + 1) * wplane, 0));
+        xa[slot][0] = a3d_load4(rx, xoff, c * 64);
+        xa[slot][1] = a3d_load4(rx, xoff, c * 64 + 16);
+        wf[slot][0] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, woff, (2 * c) * wplane, 0));
+        wf[slot][1] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, woff, (2 * c + 1) * wplane, 0));
     };
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     // One chunk = three dependent MFMAs on the one accumulator (32 matrix-pipe cycles each) and ~26 VALU instructions of split: the split
     // of chunk c + 1 is placed in the shadows of chunk c's products.
-    sg_h16x8 xh, xl, nxh, nxl;
-    auto split = [&](const int slot, sg_h16x8 &h, sg_h16x8 &l) {
-        sg_h16x4 h0, l0, h1, l1;
-        sg_split(xa[slot][0], sx, h0, l0);
-        sg_split(xa[slot][1], sx, h1, l1);
+    h16x8 xh, xl, nxh, nxl;
+    auto split = [&](const int slot, h16x8 &h, h16x8 &l) {
+        h16x4 h0, l0, h1, l1;
+        a3d_split2h(xa[slot][0], sx, h0, l0);
+        a3d_split2h(xa[slot][1], sx, h1, l1);
         h = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
         l = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
     };

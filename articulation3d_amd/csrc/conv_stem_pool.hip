@@ -20,8 +20,6 @@
 #include <stdlib.h>
 
 namespace {
-typedef _Float16 sp_h16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 sp_h16x8 __attribute__((ext_vector_type(8)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SP_NKC = 14;  // 16-deep chunks: 7 filter rows x 2 column halves
@@ -58,9 +56,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void stem_pool_kernel(con
     const int khalf = lane >> 5, frow = lane & 31;
 
     // ---- the wave's filter fragments: w_x3 [chunk][plane][64][16] fp16, row nb * 32 + lane % 32, k half lane / 32
-    sp_h16x8 Wf[SP_NKC][2];
+    h16x8 Wf[SP_NKC][2];
     {
-        const sp_h16x8 *w = reinterpret_cast<const sp_h16x8 *>(d.w_x3);
+        const h16x8 *w = reinterpret_cast<const h16x8 *>(d.w_x3);
 #pragma unroll
         for (int kc = 0; kc < SP_NKC; ++kc)
 #pragma unroll
@@ -77,7 +75,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void stem_pool_kernel(con
         const int cy = qc / SP_CW, cx = qc - cy * SP_CW;
         bbase[j] = ((2 * cy) * SP_IW + 2 * cx + 2 * khalf) * 8;  // bytes: patch pixel of filter tap (0, 2 khalf) of this conv pixel
     }
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(d.x), 0, (int)((size_t)d.B * d.H * d.W * 16), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = a3d_rsrc(d.x, (unsigned)((size_t)d.B * d.H * d.W * 16));
     const float unw = 1.f / d.w_scale;
     const bool relu = d.act == A3D_ACT_RELU;
     const int tpi = tiles_x * tiles_y;
@@ -107,7 +105,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void stem_pool_kernel(con
             const int r = j / SP_IW, c = j - r * SP_IW;
             const int y = iy0 + r, x = ix0 + c;
             const bool inb = t < total && j < SP_NPIX && (unsigned)y < (unsigned)d.H && (unsigned)x < (unsigned)d.W;
-            xs[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, inb ? ((b * d.H + y) * d.W + x) * 16 : -1, 0, 0));
+            xs[i] = a3d_load4(rx, inb ? ((b * d.H + y) * d.W + x) * 16 : -1, 0);
         }
     };
     // a workgroup walks a CONTIGUOUS range of tiles: the image changes a couple of times per workgroup, so the two things that depend on
@@ -125,11 +123,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void stem_pool_kernel(con
         for (int i = 0; i < SP_LI; ++i) {
             const int j = tid + NT * i;
             if (j >= SP_NPIX) continue;
-            const f32x4 v = xs[i] * sx;
-            const sp_h16x4 h = __builtin_convertvector(v, sp_h16x4);
-            const sp_h16x4 l = __builtin_convertvector(v - __builtin_convertvector(h, f32x4), sp_h16x4);
-            *reinterpret_cast<sp_h16x4 *>(Xh + j * 8) = h;
-            *reinterpret_cast<sp_h16x4 *>(Xl + j * 8) = l;
+            h16x4 h, l;
+            a3d_split2h(xs[i], sx, h, l);
+            *reinterpret_cast<h16x4 *>(Xh + j * 8) = h;
+            *reinterpret_cast<h16x4 *>(Xl + j * 8) = l;
         }
     };
     // Order inside an iteration: [barrier] conv of tile t, [barrier] patch of tile t + 1 into LDS, pool + stores of tile t, loads of
@@ -165,13 +162,13 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void stem_pool_kernel(con
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-            sp_h16x8 bh[2][2], bl[2][2];  // [chunk parity][block]
+            h16x8 bh[2][2], bl[2][2];  // [chunk parity][block]
             auto rd = [&](const int kc, const int set) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int off = bbase[j] + ((kc >> 1) * SP_IW + 4 * (kc & 1)) * 8;
-                    bh[set][j] = *reinterpret_cast<const sp_h16x8 *>(Xh + off);
-                    bl[set][j] = *reinterpret_cast<const sp_h16x8 *>(Xl + off);
+                    bh[set][j] = *reinterpret_cast<const h16x8 *>(Xh + off);
+                    bl[set][j] = *reinterpret_cast<const h16x8 *>(Xl + off);
                 }
             };
 #ifdef A3D_ABLATIONS

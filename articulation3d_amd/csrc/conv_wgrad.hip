@@ -12,7 +12,7 @@
 // Workgroup = 128 (co) x 128 (ci) x one tap x one pixel slice; 4 waves as 2x2, each 64x64 (4 accumulators).  Pixel
 // slices (split-K) write partials to the workspace; a second launch sums them in slice order (deterministic), applies
 // the folded-BN scale and stores or accumulates into dw, which has the packed forward layout [Cout][KH][KW][Cin].
-#include "a3d_common.h"
+#include "conv_prims.h"
 #include "../../include/a3d.h"
 
 namespace {
@@ -160,17 +160,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_batch_kernel(const a3d_
 // contiguous bytes per pixel), rounds the 8 values to bf16 and writes them as one 16-byte row segment of the LDS image
 // [channel][32 pixels] (80-byte pitch: conflict-free ds_write_b128 / ds_read_b128).  Chunk = 32 pixels.
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float wg_f32x8 __attribute__((ext_vector_type(8)));
-
-// x == h + m + l exactly (round-to-nearest-even at each level): the 3-way split of csrc/conv_bf16x3.hip, 8 wide
-__device__ __forceinline__ void wg_split3(const wg_f32x8 v, wg_bf16x8 &h, wg_bf16x8 &m, wg_bf16x8 &l) {
-    h = __builtin_convertvector(v, wg_bf16x8);
-    const wg_f32x8 r1 = v - __builtin_convertvector(h, wg_f32x8);
-    m = __builtin_convertvector(r1, wg_bf16x8);
-    const wg_f32x8 r2 = r1 - __builtin_convertvector(m, wg_f32x8);
-    l = __builtin_convertvector(r2, wg_bf16x8);
-}
 
 // X3 = false: precision 1 (operands rounded to bf16, chunk of 32 pixels).  X3 = true: precision 2, fp32-grade -- both
 // operands split exactly into hi | mid | lo bf16 planes in LDS and six MFMAs per 16-pixel k step (conv_bf16x3.hip has the
@@ -200,15 +189,15 @@ __global__ __launch_bounds__(256, X3 ? 2 : 3) void conv_wgrad_bf16_kernel(const 
     const int HoWo = d.Ho * d.Wo;
     static_assert(!X3 || IO == 0, "bf16-stored operands belong to the bf16 arithmetic");
     constexpr bool xb = IO & 1, yb = IO & 2;  // operands stored as bf16
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(d.dy), 0, (int)(((size_t)P * d.Cout * 4) >> (yb ? 1 : 0)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t ry = a3d_rsrc(d.dy, (unsigned)(((size_t)P * d.Cout * 4) >> (yb ? 1 : 0)));
     const __amdgpu_buffer_rsrc_t rx =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(d.x), 0, (int)(((size_t)d.B * d.H * d.W * d.Cin * 4) >> (xb ? 1 : 0)), 0x00020000);
+        a3d_rsrc(d.x, (unsigned)(((size_t)d.B * d.H * d.W * d.Cin * 4) >> (xb ? 1 : 0)));
     // fp32-stored operand: a thread owns ONE channel (tid % 128) for G groups of 8 pixels: 8 G dword loads, rounded to bf16 on the way
     // into LDS.  bf16-stored operand (X3 = false only): a thread owns a channel PAIR (tid % 64) for ONE group of 8 pixels (tid / 64):
     // 8 dword loads -- half as many, each still a full dword -- whose low / high halves are the two channels' pixels; no conversion.
     const int cp = tid & 63, pg16 = tid >> 6;
     const bool a_ok2 = co0 + 2 * cp + 1 < d.Cout, b_ok2 = ci0 + 2 * cp + 1 < d.Cin;
-    wg_f32x8 ra[G], rb[G];
+    f32x8 ra[G], rb[G];
     unsigned qa[8], qb[8];
     auto load = [&](int p0) {
         if constexpr (!yb || !xb || X3) {
@@ -281,18 +270,18 @@ __global__ __launch_bounds__(256, X3 ? 2 : 3) void conv_wgrad_bf16_kernel(const 
         for (int g = 0; g < G; ++g) {
             const int off = ch * LKB + (kg * G + g) * 8;
             if constexpr (X3) {
-                wg_bf16x8 h, m, l;
-                wg_split3(ra[g], h, m, l);
-                *reinterpret_cast<wg_bf16x8 *>(&lds[buf][0][off]) = h;
-                *reinterpret_cast<wg_bf16x8 *>(&lds[buf][0][PL + off]) = m;
-                *reinterpret_cast<wg_bf16x8 *>(&lds[buf][0][2 * PL + off]) = l;
-                wg_split3(rb[g], h, m, l);
-                *reinterpret_cast<wg_bf16x8 *>(&lds[buf][1][off]) = h;
-                *reinterpret_cast<wg_bf16x8 *>(&lds[buf][1][PL + off]) = m;
-                *reinterpret_cast<wg_bf16x8 *>(&lds[buf][1][2 * PL + off]) = l;
+                bf16x8 h, m, l;
+                a3d_split3(ra[g], h, m, l);
+                *reinterpret_cast<bf16x8 *>(&lds[buf][0][off]) = h;
+                *reinterpret_cast<bf16x8 *>(&lds[buf][0][PL + off]) = m;
+                *reinterpret_cast<bf16x8 *>(&lds[buf][0][2 * PL + off]) = l;
+                a3d_split3(rb[g], h, m, l);
+                *reinterpret_cast<bf16x8 *>(&lds[buf][1][off]) = h;
+                *reinterpret_cast<bf16x8 *>(&lds[buf][1][PL + off]) = m;
+                *reinterpret_cast<bf16x8 *>(&lds[buf][1][2 * PL + off]) = l;
             } else {
-                if constexpr (!yb) *reinterpret_cast<wg_bf16x8 *>(&lds[buf][0][off]) = __builtin_convertvector(ra[g], wg_bf16x8);
-                if constexpr (!xb) *reinterpret_cast<wg_bf16x8 *>(&lds[buf][1][off]) = __builtin_convertvector(rb[g], wg_bf16x8);
+                if constexpr (!yb) *reinterpret_cast<bf16x8 *>(&lds[buf][0][off]) = __builtin_convertvector(ra[g], bf16x8);
+                if constexpr (!xb) *reinterpret_cast<bf16x8 *>(&lds[buf][1][off]) = __builtin_convertvector(rb[g], bf16x8);
             }
         }
     };
@@ -318,13 +307,13 @@ __global__ __launch_bounds__(256, X3 ? 2 : 3) void conv_wgrad_bf16_kernel(const 
         const __bf16 *Bm = &lds[cur][1][(wn * 64) * LKB + foff];
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            wg_bf16x8 a[NPL][2], b[NPL][2];
+            bf16x8 a[NPL][2], b[NPL][2];
 #pragma unroll
             for (int p = 0; p < NPL; ++p)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    a[p][i] = *reinterpret_cast<const wg_bf16x8 *>(A + p * PL + i * 32 * LKB + s * 16);
-                    b[p][i] = *reinterpret_cast<const wg_bf16x8 *>(Bm + p * PL + i * 32 * LKB + s * 16);
+                    a[p][i] = *reinterpret_cast<const bf16x8 *>(A + p * PL + i * 32 * LKB + s * 16);
+                    b[p][i] = *reinterpret_cast<const bf16x8 *>(Bm + p * PL + i * 32 * LKB + s * 16);
                 }
 #define WG_TERM(PA, PB)                                                                                  \
     _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = \

@@ -20,14 +20,12 @@
 // The partial sums go to the same workspace layout [slice][co][tap][ci] as the first form's: the slice reduction (per launch or
 // batched) is unchanged.  Products are the same bf16 roundings of the same values; the summation order over pixels differs from the
 // first form's (other chunk and slice boundaries), i.e. results agree to fp32 rounding of the sums, not bit for bit.
-#include "a3d_common.h"
+#include "conv_prims.h"
 #include "../../include/a3d.h"
 
 namespace {
 typedef short tr_s16x4 __attribute__((ext_vector_type(4)));
 typedef short tr_s16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 tr_bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 tr_bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned tr_u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) tr_s16x4 *tr_lds_ptr;
 
@@ -73,8 +71,8 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_wgrad_tr_kernel(const a3
     const int p_begin = blockIdx.y * chunk, p_end = min(Ppl, p_begin + chunk);
     const int nchunks = (p_end - p_begin + TR_CH - 1) / TR_CH;
 
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(d.dy), 0, (int)(((size_t)d.B * d.Ho * d.Wo * d.Cout * 4) >> (YB ? 1 : 0)), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(d.x), 0, (int)(((size_t)d.B * d.H * d.W * d.Cin * 4) >> (XB ? 1 : 0)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t ry = a3d_rsrc(d.dy, (unsigned)(((size_t)d.B * d.Ho * d.Wo * d.Cout * 4) >> (YB ? 1 : 0)));
+    const __amdgpu_buffer_rsrc_t rx = a3d_rsrc(d.x, (unsigned)(((size_t)d.B * d.H * d.W * d.Cin * 4) >> (XB ? 1 : 0)));
 
     // ---- loaders: thread = (row tid / PPR + RPP i, piece tid % PPR) of each operand
     const int pa = tid % PPR_A, ra0 = tid / PPR_A, pb = tid % PPR_B, rb0 = tid / PPR_B;
@@ -119,7 +117,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_wgrad_tr_kernel(const a3
         for (int i = 0; i < NA; ++i) {
             unsigned char *p = A + (ra0 + RPP_A * i) * RA + wa;
             if constexpr (YB) *reinterpret_cast<tr_u32x4 *>(p) = ga[i];
-            else *reinterpret_cast<tr_bf16x4 *>(p) = __builtin_convertvector(__builtin_bit_cast(f32x4, ga[i]), tr_bf16x4);
+            else *reinterpret_cast<bf16x4 *>(p) = __builtin_convertvector(__builtin_bit_cast(f32x4, ga[i]), bf16x4);
         }
 #pragma unroll
         for (int i = 0; i < NBP; ++i) {
@@ -127,7 +125,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_wgrad_tr_kernel(const a3
             if (NBP * RPP_B > ROWS_B && row >= ROWS_B) continue;
             unsigned char *p = Bp + row * RB + wb;
             if constexpr (XB) *reinterpret_cast<tr_u32x4 *>(p) = gb[i];
-            else *reinterpret_cast<tr_bf16x4 *>(p) = __builtin_convertvector(__builtin_bit_cast(f32x4, gb[i]), tr_bf16x4);
+            else *reinterpret_cast<bf16x4 *>(p) = __builtin_convertvector(__builtin_bit_cast(f32x4, gb[i]), bf16x4);
         }
     };
 
@@ -169,18 +167,18 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_wgrad_tr_kernel(const a3
         if (c + 1 < nchunks) load(p_begin + (c + 1) * TR_CH);
 #pragma unroll
         for (int ks = 0; ks < TR_CH / 16; ++ks) {
-            tr_bf16x8 a[MB], b[NT][NB];
+            bf16x8 a[MB], b[NT][NB];
 #pragma unroll
             for (int i = 0; i < MB; ++i) {
                 const tr_s16x4 lo = frag(fa[i] + st, RA * (16 * ks)), hi = frag(fa[i] + st, RA * (16 * ks + 4));
-                a[i] = __builtin_bit_cast(tr_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                a[i] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
             }
 #pragma unroll
             for (int s = 0; s < NT; ++s)
 #pragma unroll
                 for (int j = 0; j < NB; ++j) {
                     const tr_s16x4 lo = frag(fb[s][j] + st, RB * (16 * ks)), hi = frag(fb[s][j] + st, RB * (16 * ks + 4));
-                    b[s][j] = __builtin_bit_cast(tr_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                    b[s][j] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
                 }
 #pragma unroll
             for (int s = 0; s < NT; ++s)

@@ -20,13 +20,6 @@
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ f32x4 wbuf_load4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wmake_rsrc(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
-
 // ------------------------------------------------------------------------------------------------
 // 1. input transform.  One thread = (tile, channel quad); 16 guarded float4 loads, 32+32 adds, 16 stores.
 // ------------------------------------------------------------------------------------------------
@@ -90,7 +83,6 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const float *__restrict
 // LDS-DMA wants: Vs [16 planes][C/32 chunks][h | l][T tiles][32 k] fp16.  The bytes are those of the fp32 tensor (2 + 2 per element).
 // What it buys: wino_gemm_x3w_kernel<.., F16> moves V global -> LDS without registers, without the
 // 2.7 vector instructions per MFMA the split cost there (PMC), without VGPR -> LDS stores.
-typedef _Float16 wi_h16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int wi_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int wi_u32x4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void wino_input_h2_kernel(const float *__restrict__ x, const float *__restrict__ x2, unsigned char *__restrict__ Vs,
@@ -156,11 +148,10 @@ __global__ __launch_bounds__(256) void wino_input_h2_kernel(const float *__restr
             const f32x4 vv[4] = {m[u][0] - m[u][2], m[u][1] + m[u][2], m[u][2] - m[u][1], m[u][1] - m[u][3]};
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
-                const f32x4 xs = vv[v] * sv;
-                const wi_h16x4 h = __builtin_convertvector(xs, wi_h16x4);
-                const wi_h16x4 l = __builtin_convertvector(xs - __builtin_convertvector(h, f32x4), wi_h16x4);
-                *reinterpret_cast<wi_h16x4 *>(oh) = h;
-                *reinterpret_cast<wi_h16x4 *>(oh + tile) = l;
+                h16x4 h, l;
+                a3d_split2h(vv[v], sv, h, l);
+                *reinterpret_cast<h16x4 *>(oh) = h;
+                *reinterpret_cast<h16x4 *>(oh + tile) = l;
                 oh += pstride;
             }
         }
@@ -212,8 +203,6 @@ __device__ __forceinline__ V wino_level_sel(const V (&arr)[5], const int l) {
     return v;
 }
 
-typedef _Float16 wh16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 wh16x8 __attribute__((ext_vector_type(8)));
 // power-of-two scale of the V rows of image b: |B^T d B| <= 4 max |d|
 __device__ __forceinline__ float wino_v_scale(const WinoArgs &a, const int b) {
     float m = a.in_amax[b];
@@ -263,13 +252,13 @@ __global__ __launch_bounds__(256, TN == 1 ? 3 : 1) void wino_gemm_kernel(const W
         // (the two look-ahead loads past the last chunk re-read plane 15: in range, never consumed; keeping them
         // unconditional keeps the loop body free of branches)
         const int f = min(ld_f, 15);
-        const __amdgpu_buffer_rsrc_t rv = wmake_rsrc(a.V + (size_t)f * vplane, vbytes);
-        const __amdgpu_buffer_rsrc_t ru = wmake_rsrc(a.U + (size_t)f * uplane, ubytes);
+        const __amdgpu_buffer_rsrc_t rv = a3d_rsrc(a.V + (size_t)f * vplane, vbytes);
+        const __amdgpu_buffer_rsrc_t ru = a3d_rsrc(a.U + (size_t)f * uplane, ubytes);
         const int soff = ld_kc * BKT * 4;
 #pragma unroll
-        for (int i = 0; i < XR; ++i) xs[i] = wbuf_load4(rv, xoff[i], soff);
+        for (int i = 0; i < XR; ++i) xs[i] = a3d_load4(rv, xoff[i], soff);
 #pragma unroll
-        for (int i = 0; i < WR; ++i) ws[i] = wbuf_load4(ru, woff[i], soff);
+        for (int i = 0; i < WR; ++i) ws[i] = a3d_load4(ru, woff[i], soff);
         if (++ld_kc == KC) {
             ld_kc = 0;
             ++ld_f;
@@ -424,16 +413,6 @@ __global__ __launch_bounds__(256, TN == 1 ? 3 : 1) void wino_gemm_kernel(const W
 // operand plane: [64 rows][32 k] bf16, 64-byte rows whose four 16-byte slots are XOR-swizzled with bits 2..3 of the row
 // index (conflict-free ds_read_b128 under the 64-bank / 16-lane-group rule, conflict-free ds_write_b64).
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 wbf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 wbf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void wsplit3(const f32x4 v, wbf16x4 &h, wbf16x4 &m, wbf16x4 &l) {
-    h = __builtin_convertvector(v, wbf16x4);
-    const f32x4 r1 = v - __builtin_convertvector(h, f32x4);
-    m = __builtin_convertvector(r1, wbf16x4);
-    const f32x4 r2 = r1 - __builtin_convertvector(m, f32x4);
-    l = __builtin_convertvector(r2, wbf16x4);
-}
 
 __global__ __launch_bounds__(256, 3) void wino_gemm_x3_kernel(const WinoArgs a, const int ntiles, const int nblk) {
     constexpr int TN = 1, BKT = 32;
@@ -475,13 +454,13 @@ __global__ __launch_bounds__(256, 3) void wino_gemm_x3_kernel(const WinoArgs a, 
     int ld_f = 0, ld_kc = 0;
     auto load_chunk = [&](f32x4 (&xs)[XR], f32x4 (&ws)[3]) {
         const int f = min(ld_f, 15);
-        const __amdgpu_buffer_rsrc_t rv = wmake_rsrc(a.V + (size_t)f * vplane, vbytes);
-        const __amdgpu_buffer_rsrc_t ru = wmake_rsrc(reinterpret_cast<const float *>(a.U3 + (size_t)f * 3 * uplane), (unsigned)(uplane * 6));
+        const __amdgpu_buffer_rsrc_t rv = a3d_rsrc(a.V + (size_t)f * vplane, vbytes);
+        const __amdgpu_buffer_rsrc_t ru = a3d_rsrc(reinterpret_cast<const float *>(a.U3 + (size_t)f * 3 * uplane), (unsigned)(uplane * 6));
         const int soff = ld_kc * BKT * 4;
 #pragma unroll
-        for (int i = 0; i < XR; ++i) xs[i] = wbuf_load4(rv, xoff[i], soff);
+        for (int i = 0; i < XR; ++i) xs[i] = a3d_load4(rv, xoff[i], soff);
 #pragma unroll
-        for (int p = 0; p < 3; ++p) ws[p] = wbuf_load4(ru, woff, (ld_kc * 3 + p) * (int)u3tile);
+        for (int p = 0; p < 3; ++p) ws[p] = a3d_load4(ru, woff, (ld_kc * 3 + p) * (int)u3tile);
         if (++ld_kc == KC) {
             ld_kc = 0;
             ++ld_f;
@@ -492,12 +471,12 @@ __global__ __launch_bounds__(256, 3) void wino_gemm_x3_kernel(const WinoArgs a, 
         __bf16 *Wt = X + 3 * PL;
 #pragma unroll
         for (int i = 0; i < XR; ++i) {
-            wbf16x4 h, m, l;
-            wsplit3(xs[i], h, m, l);
+            bf16x4 h, m, l;
+            a3d_split3(xs[i], h, m, l);
             __bf16 *p = X + (lr + RPP * i) * LKB + lcs;
-            *reinterpret_cast<wbf16x4 *>(p) = h;
-            *reinterpret_cast<wbf16x4 *>(p + PL) = m;
-            *reinterpret_cast<wbf16x4 *>(p + 2 * PL) = l;
+            *reinterpret_cast<bf16x4 *>(p) = h;
+            *reinterpret_cast<bf16x4 *>(p + PL) = m;
+            *reinterpret_cast<bf16x4 *>(p + 2 * PL) = l;
         }
 #pragma unroll
         for (int p = 0; p < 3; ++p) *reinterpret_cast<f32x4 *>(Wt + p * PL + wlds) = ws[p];
@@ -548,13 +527,13 @@ __global__ __launch_bounds__(256, 3) void wino_gemm_x3_kernel(const WinoArgs a, 
         const __bf16 *X = lds + cur * BUF + (wm * 32 + frow) * LKB;
         const __bf16 *Wt = lds + cur * BUF + 3 * PL + (wn * 32 + frow) * LKB;
         // fragments of ONE 16-deep step at a time (24 registers; both steps at once cost 48 and spill at 3 workgroups per CU)
-        wbf16x8 fa[3], fb[3];
+        bf16x8 fa[3], fb[3];
         auto frags = [&](const int st) {
             const int slot = (((2 * st + (lane >> 5)) ^ fsw) & 3) << 3;
 #pragma unroll
             for (int p = 0; p < 3; ++p) {
-                fa[p] = *reinterpret_cast<const wbf16x8 *>(Wt + p * PL + slot);
-                fb[p] = *reinterpret_cast<const wbf16x8 *>(X + p * PL + slot);
+                fa[p] = *reinterpret_cast<const bf16x8 *>(Wt + p * PL + slot);
+                fb[p] = *reinterpret_cast<const bf16x8 *>(X + p * PL + slot);
             }
         };
 #define WX3(PA, PB) acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[PA], fb[PB], acc[0], 0, 0, 0);
@@ -653,15 +632,6 @@ __global__ __launch_bounds__(256, 3) void wino_gemm_x3_kernel(const WinoArgs a, 
 // The per-output operation order (planes, k chunks, 16-deep steps, the six product terms) is that of wino_gemm_x3_kernel: the two
 // kernels agree bit for bit (tests/test_gpu_parity.py), so the launcher chooses by problem size.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wuni_rsrc(const void *p, unsigned bytes) {
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    void *q = reinterpret_cast<void *>(((unsigned long long)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(q, 0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-__device__ __forceinline__ void wdma16(__amdgpu_buffer_rsrc_t r, __bf16 *lds_dst, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)lds_dst, 16, voff, soff, 0, 0);
-}
 
 constexpr int X3W_BN = 128, X3W_LKB = 32;
 constexpr int x3w_buf(int WM, int NP) { return NP * (32 * WM + X3W_BN) * X3W_LKB; }  // 16-bit elements of one stage: X and W, NP planes each
@@ -728,7 +698,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void wino_gemm_x3w_kerne
     // weights: U3 [16][C/32][3][Cout][32] bf16; one (f, chunk, plane) tile of this workgroup's 128 rows is an 8 KiB run = 8 DMA
     // wave-instructions of 16 rows.  Lane i of an instruction lands at LDS byte 16 i of its 1 KiB = row i/4, slot i%4, and
     // fetches the k slot that the image keeps there: slot ^ ((row >> 2) & 3)  (row base is a multiple of 16)
-    const __amdgpu_buffer_rsrc_t ru = wuni_rsrc(a.U3, (unsigned)((size_t)16 * a.Cout * a.C * 2 * NP));
+    const __amdgpu_buffer_rsrc_t ru = a3d_rsrc_uniform(a.U3, (unsigned)((size_t)16 * a.Cout * a.C * 2 * NP));
     const int wvoff = (lane >> 2) * 64 + (((lane & 3) ^ ((lane >> 4) & 3)) << 4);
     const int u3tile = a.Cout * 64;  // bytes of one (f, chunk, plane) tile
     int dma_c = pf * KC;             // flat (f, kc) index of the next weight chunk to fetch
@@ -740,7 +710,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void wino_gemm_x3w_kerne
         for (int i = 0; i < DPW; ++i) {
             const int j = wave * DPW + i;
             const int p = j >> 3, g = j & 7;
-            wdma16(ru, Wt + p * PLW + g * 16 * LKB, wvoff, base + __builtin_amdgcn_readfirstlane(p * u3tile + g * 1024));
+            a3d_dma16(ru, Wt + p * PLW + g * 16 * LKB, wvoff, base + __builtin_amdgcn_readfirstlane(p * u3tile + g * 1024));
         }
         ++dma_c;
     };
@@ -753,46 +723,45 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void wino_gemm_x3w_kerne
     auto dma_v = [&](const int buf, const int c) {  // c = flat (f, kc) index of the chunk (clamped like the filter's)
         __bf16 *X = lds + buf * BUF;
         const size_t tile = (size_t)a.Ttot * 64;  // bytes of one (f, chunk, plane) tile (Ttot = T unless the layer's tiles are a slice)
-        const __amdgpu_buffer_rsrc_t rv = wuni_rsrc(reinterpret_cast<const char *>(a.V) + (size_t)min(c, NIT - 1) * 2 * tile, (unsigned)(2 * tile));
+        const __amdgpu_buffer_rsrc_t rv = a3d_rsrc_uniform(reinterpret_cast<const char *>(a.V) + (size_t)min(c, NIT - 1) * 2 * tile, (unsigned)(2 * tile));
 #pragma unroll
         for (int i = 0; i < DPV; ++i) {
             const int j = wave * DPV + i;
             const int p = j / (BM / 16), g = j % (BM / 16);
-            wdma16(rv, X + p * PLX + g * 16 * LKB, wvoff, __builtin_amdgcn_readfirstlane(p * (int)tile + (a.Toff + t0 + g * 16) * 64));
+            a3d_dma16(rv, X + p * PLX + g * 16 * LKB, wvoff, __builtin_amdgcn_readfirstlane(p * (int)tile + (a.Toff + t0 + g * 16) * 64));
         }
     };
     f32x4 xsA[XR], xsB[XR];
     int ld_f = pf, ld_kc = 0;
     auto load_chunk = [&](f32x4 (&xs)[XR]) {
         const int f = min(ld_f, 15);
-        const __amdgpu_buffer_rsrc_t rv = wuni_rsrc(a.V + (size_t)f * vplane, vbytes);
+        const __amdgpu_buffer_rsrc_t rv = a3d_rsrc_uniform(a.V + (size_t)f * vplane, vbytes);
         const int soff = ld_kc * BKT * 4;
 #pragma unroll
-        for (int i = 0; i < XR; ++i) xs[i] = wbuf_load4(rv, xoff[i], soff);
+        for (int i = 0; i < XR; ++i) xs[i] = a3d_load4(rv, xoff[i], soff);
         if (++ld_kc == KC) {
             ld_kc = 0;
             ++ld_f;
         }
     };
     struct Split {
-        wbf16x4 h, m, l;  // (fp16x2: h, m hold the two fp16 planes' bits)
+        bf16x4 h, m, l;  // (fp16x2: h, m hold the two fp16 planes' bits)
     };
     auto split = [&](const f32x4 v, const int i, Split &o) {
         if constexpr (F16) {
-            const f32x4 xs = v * sxr[i];
-            const wh16x4 h = __builtin_convertvector(xs, wh16x4);
-            const wh16x4 l = __builtin_convertvector(xs - __builtin_convertvector(h, f32x4), wh16x4);
-            o.h = __builtin_bit_cast(wbf16x4, h);
-            o.m = __builtin_bit_cast(wbf16x4, l);
+            h16x4 h, l;
+            a3d_split2h(v, sxr[i], h, l);
+            o.h = __builtin_bit_cast(bf16x4, h);
+            o.m = __builtin_bit_cast(bf16x4, l);
         } else {
-            wsplit3(v, o.h, o.m, o.l);
+            a3d_split3(v, o.h, o.m, o.l);
         }
     };
     auto put = [&](const int buf, const int i, const Split &v) {  // the planes of loader row lr + RPP i
         __bf16 *p = lds + buf * BUF + (lr + RPP * i) * LKB + lcs;
-        *reinterpret_cast<wbf16x4 *>(p) = v.h;
-        *reinterpret_cast<wbf16x4 *>(p + PLX) = v.m;
-        if constexpr (!F16) *reinterpret_cast<wbf16x4 *>(p + 2 * PLX) = v.l;
+        *reinterpret_cast<bf16x4 *>(p) = v.h;
+        *reinterpret_cast<bf16x4 *>(p + PLX) = v.m;
+        if constexpr (!F16) *reinterpret_cast<bf16x4 *>(p + 2 * PLX) = v.l;
     };
 
     f32x16 mf[TN];
@@ -816,16 +785,16 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void wino_gemm_x3w_kerne
     const __bf16 *fX = lds + (wm * 32 + frow) * LKB;
     const __bf16 *fW = lds + NP * PLX + (wn * 64 + frow) * LKB;
     struct Frags {
-        wbf16x8 a[NP][TN], b[NP];
+        bf16x8 a[NP][TN], b[NP];
     };
     auto rdA = [&](Frags &F, const int buf, const int st, const int p) {
         const int slot = (((2 * st + (lane >> 5)) ^ fsw) & 3) << 3;
 #pragma unroll
-        for (int n = 0; n < TN; ++n) F.a[p][n] = *reinterpret_cast<const wbf16x8 *>(fW + buf * BUF + p * PLW + n * 32 * LKB + slot);
+        for (int n = 0; n < TN; ++n) F.a[p][n] = *reinterpret_cast<const bf16x8 *>(fW + buf * BUF + p * PLW + n * 32 * LKB + slot);
     };
     auto rdB = [&](Frags &F, const int buf, const int st, const int p) {
         const int slot = (((2 * st + (lane >> 5)) ^ fsw) & 3) << 3;
-        F.b[p] = *reinterpret_cast<const wbf16x8 *>(fX + buf * BUF + p * PLX + slot);
+        F.b[p] = *reinterpret_cast<const bf16x8 *>(fX + buf * BUF + p * PLX + slot);
     };
     auto fold = [&](f32x16 (&m)[TN], const int f) {
         const int u = f >> 2, v = f & 3;
@@ -860,7 +829,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void wino_gemm_x3w_kerne
     // (timing-only ablation: 3.80 -> 2.69 ms without the reads).
 #define X3W_FENCE __builtin_amdgcn_sched_barrier(0);
 #define X3W_MFMA(C, A, Bv)                                                                                                                \
-    if constexpr (F16) C = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wh16x8, A), __builtin_bit_cast(wh16x8, Bv), C, 0, 0, 0); \
+    if constexpr (F16) C = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, A), __builtin_bit_cast(h16x8, Bv), C, 0, 0, 0); \
     else C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, Bv, C, 0, 0, 0);
 #define X3W_TERM(F, PA, PB)              \
     X3W_MFMA(mf[0], F.a[PA][0], F.b[PB]) \
@@ -987,7 +956,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void wino_gemm_x3w_kerne
             dma_v(i, dma_c);
             dma_w(i);
         }
-        __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 1) * OPS) : "memory");
+        a3d_wait_vm<(NST - 1) * OPS>();
         __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (scale / shift staged above)
         __builtin_amdgcn_s_barrier();
 #pragma unroll
@@ -1071,7 +1040,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void wino_gemm_x3w_kerne
 #else
                 if (grpB) {
 #endif
-                    __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * OPSP) : "memory");
+                    a3d_wait_vm<(NST - 2) * OPSP>();
                     __builtin_amdgcn_s_barrier();
                 }
 #ifdef A3D_ABLATIONS
@@ -1083,7 +1052,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void wino_gemm_x3w_kerne
 #else
                 if (!grpB) {
 #endif
-                    __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * OPSP) : "memory");
+                    a3d_wait_vm<(NST - 2) * OPSP>();
                     __builtin_amdgcn_s_barrier();
                 }
                 advance();
@@ -1112,7 +1081,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void wino_gemm_x3w_kerne
             if (rd) rdA(F1, st, 1, 1);
             X3W_TERM(F0, 1, 0)
             X3W_FENCE
-            __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * OPS) : "memory");
+            a3d_wait_vm<(NST - 2) * OPS>();
             __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (!(a.abl & 4)) __builtin_amdgcn_s_barrier();
             if (!(a.abl & 1)) dma_v(st, dma_c);
@@ -1145,7 +1114,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void wino_gemm_x3w_kerne
             rdA(F1, st, 1, 1);
             X3W_TERM(F0, 1, 0)
             X3W_FENCE
-            __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * OPS) : "memory");  // chunk it + 1 has landed (younger: NST - 2 chunks)
+            a3d_wait_vm<(NST - 2) * OPS>();  // chunk it + 1 has landed (younger: NST - 2 chunks)
             __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             dma_v(st, dma_c);  // chunk it + NST into the stage of chunk it
@@ -1241,6 +1210,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void wino_gemm_x3w_kerne
 #pragma unroll
             for (int rg = 0; rg < 4; ++rg) {
                 const f32x4 v = {mf[ni][rg * 4 + 0], mf[ni][rg * 4 + 1], mf[ni][rg * 4 + 2], mf[ni][rg * 4 + 3]};
+                // (the tile turn stays spelled out: behind a3d_turn_put / a3d_turn_get this kernel's register allocation and instruction order changed)
                 *reinterpret_cast<f32x4 *>(Tt + pr * 32 + (((rg * 2 + ph) ^ (pr & 7)) << 2)) = v;
             }
             const int n = n0 + wn * 64 + ni * 32 + qc * 4;
@@ -1371,10 +1341,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void wino_gemm_x3w_kerne
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float v = vmax[j];
-                v = fmaxf(v, __shfl_xor(v, 1, 64));
-                v = fmaxf(v, __shfl_xor(v, 2, 64));
-                v = fmaxf(v, __shfl_xor(v, 4, 64));
+                const float v = a3d_max8(vmax[j]);
                 if (jb[j] >= 0 && qc == 0 && jya[j] && v > jya[j][jb[j]]) atomicMax(reinterpret_cast<int *>(jya[j] + jb[j]), __float_as_int(v));
             }
         }
@@ -1386,13 +1353,8 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void wino_gemm_x3w_kerne
             a3d_note_amax(a.y_amax, tb / tyx, fmaxf(fmaxf(vmax[0], vmax[1]), fmaxf(vmax[2], vmax[3])), true);
         } else {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {  // (the 8 lanes of a tile reduce first: one pre-checked atomic per tile, not eight)
-                float v = vmax[j];
-                v = fmaxf(v, __shfl_xor(v, 1, 64));
-                v = fmaxf(v, __shfl_xor(v, 2, 64));
-                v = fmaxf(v, __shfl_xor(v, 4, 64));
-                a3d_note_amax(a.y_amax, max(jb[j], 0), v, jb[j] >= 0 && qc == 0);
-            }
+            // (the 8 lanes of a tile reduce first: one pre-checked atomic per tile, not eight)
+            for (int j = 0; j < 4; ++j) a3d_note_amax(a.y_amax, max(jb[j], 0), a3d_max8(vmax[j]), jb[j] >= 0 && qc == 0);
         }
     }
 }
@@ -1464,12 +1426,12 @@ __global__ __launch_bounds__(256) void split_bf16x3_kernel(const float *__restri
     const size_t per = (size_t)rows * cols;
     const size_t o = i / per, r = i - o * per;
     const int n = (int)(r / cols), c = (int)(r - (size_t)n * cols);
-    wbf16x4 h, m, l;
-    wsplit3(*reinterpret_cast<const f32x4 *>(src + i), h, m, l);
+    bf16x4 h, m, l;
+    a3d_split3(*reinterpret_cast<const f32x4 *>(src + i), h, m, l);
     __bf16 *d = dst + o * 3 * per + ((size_t)(c / chunk) * 3 * rows + n) * chunk + (c % chunk);
-    *reinterpret_cast<wbf16x4 *>(d) = h;
-    *reinterpret_cast<wbf16x4 *>(d + (size_t)rows * chunk) = m;
-    *reinterpret_cast<wbf16x4 *>(d + (size_t)rows * chunk * 2) = l;
+    *reinterpret_cast<bf16x4 *>(d) = h;
+    *reinterpret_cast<bf16x4 *>(d + (size_t)rows * chunk) = m;
+    *reinterpret_cast<bf16x4 *>(d + (size_t)rows * chunk * 2) = l;
 }
 
 extern "C" int a3d_split_bf16x3_chunk(const float *src, void *dst, int outer, int rows, int cols, int chunk, void *stream) {
@@ -1489,12 +1451,11 @@ __global__ __launch_bounds__(256) void split_f16x2_kernel(const float *__restric
     const size_t per = (size_t)rows * cols;
     const size_t o = i / per, r = i - o * per;
     const int n = (int)(r / cols), c = (int)(r - (size_t)n * cols);
-    const f32x4 xs = *reinterpret_cast<const f32x4 *>(src + i) * scale;
-    const wh16x4 h = __builtin_convertvector(xs, wh16x4);
-    const wh16x4 l = __builtin_convertvector(xs - __builtin_convertvector(h, f32x4), wh16x4);
+    h16x4 h, l;
+    a3d_split2h(*reinterpret_cast<const f32x4 *>(src + i), scale, h, l);
     _Float16 *d = dst + o * 2 * per + ((size_t)(c / chunk) * 2 * rows + n) * chunk + (c % chunk);
-    *reinterpret_cast<wh16x4 *>(d) = h;
-    *reinterpret_cast<wh16x4 *>(d + (size_t)rows * chunk) = l;
+    *reinterpret_cast<h16x4 *>(d) = h;
+    *reinterpret_cast<h16x4 *>(d + (size_t)rows * chunk) = l;
 }
 
 extern "C" int a3d_split_f16x2_chunk(const float *src, void *dst, int outer, int rows, int cols, int chunk, float scale, void *stream) {

@@ -54,20 +54,7 @@ __device__ __forceinline__ void a3d_static_for(F &&fn) {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// (base pointer and size pass through v_readfirstlane: they ARE wave-uniform, and saying so keeps the descriptor in SGPRs --
-// otherwise hipcc wraps every buffer load of the unrolled loop in a waterfall loop)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t fmake_rsrc(const void *p, unsigned bytes) {
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    void *q = reinterpret_cast<void *>(((unsigned long long)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(q, 0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
 __device__ __forceinline__ int funi(int v) { return __builtin_amdgcn_readfirstlane(v); }
-// (default cache policy on purpose: `nt` on the pixel stream was measured 1-6 % slower -- a staged line is re-used by the next
-// three chunks and by the three other channel tiles of the block)
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, float *lds_dst, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)lds_dst, 16, voff, soff, 0, 0);
-}
 
 struct WinoFusedArgs {
     const float *x;      // [B, H, W, C] NHWC
@@ -107,7 +94,7 @@ __global__ __launch_bounds__(256, 1) void wino_fused_kernel(const WinoFusedArgs 
     const int y0 = 2 * by * BH, x0 = 2 * bx * BW;                   // first output pixel of the block
 
     // ---- DMA role: slot s = 16 bytes = (pixel s >> 1 of the region, channels 4 (s & 1) .. +3); wave w issues instructions w + 4i ----
-    const __amdgpu_buffer_rsrc_t rx = fmake_rsrc(a.x, (unsigned)((size_t)a.B * a.H * a.W * a.C * 4));
+    const __amdgpu_buffer_rsrc_t rx = a3d_rsrc_uniform(a.x, (unsigned)((size_t)a.B * a.H * a.W * a.C * 4));
     int svoff[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -117,20 +104,22 @@ __global__ __launch_bounds__(256, 1) void wino_fused_kernel(const WinoFusedArgs 
         const bool ok = s < P2 && (unsigned)py < (unsigned)a.H && (unsigned)px < (unsigned)a.W;
         svoff[i] = ok ? (((b * a.H + py) * a.W + px) * a.C + (s & 1) * 4) * 4 : -1;
     }
+    // (default cache policy on purpose: `nt` on the pixel stream was measured 1-6 % slower -- a staged line is re-used by the next
+    // three chunks and by the three other channel tiles of the block)
     auto dma_patch = [&](int c, int buf) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            if ((wave + 4 * i) * 64 < P2) dma16(rx, Sl + buf * STG + (wave + 4 * i) * 256, svoff[i], funi(c * BKC * 4));
+            if ((wave + 4 * i) * 64 < P2) a3d_dma16(rx, Sl + buf * STG + (wave + 4 * i) * 256, svoff[i], funi(c * BKC * 4));
     };
     const int NT = (a.Cout + BN - 1) / BN;
     const int uchunk = 16 * NT * 512 * 4;            // bytes between consecutive chunks of Uc
-    const __amdgpu_buffer_rsrc_t ru = fmake_rsrc(a.Uc, (unsigned)((size_t)NCH * uchunk));
+    const __amdgpu_buffer_rsrc_t ru = a3d_rsrc_uniform(a.Uc, (unsigned)((size_t)NCH * uchunk));
     auto dma_u = [&](int c, int buf, int i0, int i1) {  // 32 half planes per chunk, 8 per wave
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             if (i < i0 || i >= i1) continue;
             const int hp = wave * 8 + i;
-            dma16(ru, Ul + buf * OPBUF + hp * HALF, lane * 16, funi(c * uchunk + ((hp >> 1) * NT + nt) * 2048 + (hp & 1) * 1024));
+            a3d_dma16(ru, Ul + buf * OPBUF + hp * HALF, lane * 16, funi(c * uchunk + ((hp >> 1) * NT + nt) * 2048 + (hp & 1) * 1024));
         }
     };
 

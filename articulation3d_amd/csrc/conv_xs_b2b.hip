@@ -25,31 +25,6 @@
 #include "conv_common.h"
 
 namespace {
-typedef _Float16 bb_h16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 bb_h16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bb_b16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bb_b16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t bb_rsrc(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void bb_split2h(const f32x4 v, const float s, bb_h16x4 &h, bb_h16x4 &l) {  // conv_xs_h2.hip xs_split
-    const f32x4 xs = v * s;
-    h = __builtin_convertvector(xs, bb_h16x4);
-    const f32x4 r = xs - __builtin_convertvector(h, f32x4);
-    l = __builtin_convertvector(r, bb_h16x4);
-}
-__device__ __forceinline__ void bb_split3(const f32x4 v, bb_b16x4 &h, bb_b16x4 &m, bb_b16x4 &l) {  // conv_bf16x3.hip split3
-    h = __builtin_convertvector(v, bb_b16x4);
-    const f32x4 r1 = v - __builtin_convertvector(h, f32x4);
-    m = __builtin_convertvector(r1, bb_b16x4);
-    const f32x4 r2 = r1 - __builtin_convertvector(m, f32x4);
-    l = __builtin_convertvector(r2, bb_b16x4);
-}
-template <int N>
-__device__ __forceinline__ void bb_wait_vm() {
-    __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 constexpr int BB_NST = 7;        // ring stages of 8 KiB
 constexpr int BB_D = BB_NST - 1;  // a stage's DMA is issued this many steps before its fragments are read
@@ -90,8 +65,8 @@ __global__ __launch_bounds__(256, 2) void conv_xs_b2b_kernel(const a3d_conv_desc
     const int Q = nsteps * S;
     const int Cout2 = 32 * N2T;
 
-    const __amdgpu_buffer_rsrc_t rw = bb_rsrc(d.w_x3, (unsigned)((size_t)KC * d.Cout * 64));
-    const __amdgpu_buffer_rsrc_t rw2 = bb_rsrc(e.w2, (unsigned)((size_t)(d.Cout / 16) * 3 * Cout2 * 32));
+    const __amdgpu_buffer_rsrc_t rw = a3d_rsrc(d.w_x3, (unsigned)((size_t)KC * d.Cout * 64));
+    const __amdgpu_buffer_rsrc_t rw2 = a3d_rsrc(e.w2, (unsigned)((size_t)(d.Cout / 16) * 3 * Cout2 * 32));
     const int wvoff = (lane >> 1) * 32 + (((lane & 1) ^ ((lane >> 4) & 1)) << 4);
     const int uw = __builtin_amdgcn_readfirstlane(wave);
     int dma_q = 0, dma_st = 0, rd_st = 0;
@@ -108,8 +83,7 @@ __global__ __launch_bounds__(256, 2) void conv_xs_b2b_kernel(const a3d_conv_desc
                 const int kl = j / (2 * NG), p = (j / NG) & 1, g = j % NG;
                 const int c = sp * KS + kl;
                 const int soff = live ? ((c * 2 + p) * d.Cout + ns * BN + g * 32) * 32 : 0;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void *)(st + j * 1024), 16, live ? wvoff : -1,
-                                                         __builtin_amdgcn_readfirstlane(soff), 0, 0);
+                a3d_dma16(rw, st + j * 1024, live ? wvoff : -1, __builtin_amdgcn_readfirstlane(soff));
             }
         } else {  // a stage of the second filter: chunk (ns * BN) / 16 + 2 g + ci, tile pair tp; pieces [plane][tile of the pair]
             const int i2 = sp - SPT;
@@ -122,8 +96,7 @@ __global__ __launch_bounds__(256, 2) void conv_xs_b2b_kernel(const a3d_conv_desc
                 const int p = j >> 1, tl = j & 1;
                 const bool on = live && j < 6;
                 const int soff = on ? ((c * 3 + p) * Cout2 + (tp * 2 + tl) * 32) * 32 : 0;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw2, (__attribute__((address_space(3))) void *)(st + j * 1024), 16, on ? wvoff : -1,
-                                                         __builtin_amdgcn_readfirstlane(soff), 0, 0);
+                a3d_dma16(rw2, st + j * 1024, on ? wvoff : -1, __builtin_amdgcn_readfirstlane(soff));
             }
         }
     };
@@ -139,22 +112,22 @@ __global__ __launch_bounds__(256, 2) void conv_xs_b2b_kernel(const a3d_conv_desc
     const int mp = m0 + (lane & 31);
     const bool mok = mp < M;
     const float sx = mok ? a3d_in_scale(d, mp / hwo) : 1.f;
-    bb_h16x8 xh[KC], xl[KC];
+    h16x8 xh[KC], xl[KC];
     {
-        const __amdgpu_buffer_rsrc_t rx = bb_rsrc(d.x, (unsigned)((size_t)M * d.Cin * 4));
+        const __amdgpu_buffer_rsrc_t rx = a3d_rsrc(d.x, (unsigned)((size_t)M * d.Cin * 4));
         const int voff = mok ? (mp * d.Cin + (lane >> 5) * 8) * 4 : -1;
         f32x4 raw[KC][2];
 #pragma unroll
         for (int c = 0; c < KC; ++c) {
-            raw[c][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, voff, c * 64, 0));
-            raw[c][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, voff, c * 64 + 16, 0));
+            raw[c][0] = a3d_load4(rx, voff, c * 64);
+            raw[c][1] = a3d_load4(rx, voff, c * 64 + 16);
         }
-        bb_wait_vm<0>();
+        a3d_wait_vm<0>();
 #pragma unroll
         for (int c = 0; c < KC; ++c) {
-            bb_h16x4 h0, l0, h1, l1;
-            bb_split2h(raw[c][0], sx, h0, l0);
-            bb_split2h(raw[c][1], sx, h1, l1);
+            h16x4 h0, l0, h1, l1;
+            a3d_split2h(raw[c][0], sx, h0, l0);
+            a3d_split2h(raw[c][1], sx, h1, l1);
             xh[c] = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
             xl[c] = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
         }
@@ -182,8 +155,8 @@ __global__ __launch_bounds__(256, 2) void conv_xs_b2b_kernel(const a3d_conv_desc
     // then stricter than it has to be (a few of the youngest DMAs must land early), never too weak.
     auto enter = [&](const int s) -> const unsigned char * {  // s = the step's position in the N step (a constant after unrolling)
         // (without PREF the N step's own rows go out at its start, position 0)
-        if (((s - (PREF ? SPT : 0)) % S + S) % S < BB_D) bb_wait_vm<2 * (BB_D - 1) + R>();
-        else bb_wait_vm<2 * (BB_D - 1)>();
+        if (((s - (PREF ? SPT : 0)) % S + S) % S < BB_D) a3d_wait_vm<2 * (BB_D - 1) + R>();
+        else a3d_wait_vm<2 * (BB_D - 1)>();
         // (a bare barrier: __syncthreads() carries a fence, and the compiler completes every LDS-DMA in flight in front of a fence)
         __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -196,14 +169,14 @@ __global__ __launch_bounds__(256, 2) void conv_xs_b2b_kernel(const a3d_conv_desc
     // step's second GEMM): a wave then has loads in flight through both GEMMs, not only through the first -- the launch is HBM-bound and
     // what it lacks is bytes in flight.  Buffer loads: the request past the last N step is out of range (no traffic, zeros nobody reads),
     // so every N step issues the same operations.
-    const __amdgpu_buffer_rsrc_t rres = bb_rsrc(d.res, (unsigned)((size_t)M * d.Cout * 4));
+    const __amdgpu_buffer_rsrc_t rres = a3d_rsrc(d.res, (unsigned)((size_t)M * d.Cout * 4));
     f32x4 rvA[NG][4], rvB[NG][4];  // the residual rows of even | odd N steps (two named sets: a copy would wait for the loads where it stands)
     auto load_res = [&](f32x4 (&rvn)[NG][4], const int ns) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int voff = ns < nsteps ? (min(m0 + qr + 8 * j, M - 1) * d.Cout + ns * BN + qc * 4) * 4 : -1;
 #pragma unroll
-            for (int g = 0; g < NG; ++g) rvn[g][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rres, voff, g * 128, 0));
+            for (int g = 0; g < NG; ++g) rvn[g][j] = a3d_load4(rres, voff, g * 128);
         }
     };
     if constexpr (PREF) load_res(rvA, 0);
@@ -229,11 +202,11 @@ __global__ __launch_bounds__(256, 2) void conv_xs_b2b_kernel(const a3d_conv_desc
 #pragma unroll
             for (int kl = 0; kl < KS; ++kl) {
                 const int c = t * KS + kl;
-                bb_h16x8 fa[2][NG];
+                h16x8 fa[2][NG];
 #pragma unroll
                 for (int p = 0; p < 2; ++p)
 #pragma unroll
-                    for (int g = 0; g < NG; ++g) fa[p][g] = *reinterpret_cast<const bb_h16x8 *>(st + ((kl * 2 + p) * NG + g) * 1024);
+                    for (int g = 0; g < NG; ++g) fa[p][g] = *reinterpret_cast<const h16x8 *>(st + ((kl * 2 + p) * NG + g) * 1024);
 #pragma unroll
                 for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[0][g], xh[c], acc[g], 0, 0, 0);
 #pragma unroll
@@ -251,14 +224,14 @@ __global__ __launch_bounds__(256, 2) void conv_xs_b2b_kernel(const a3d_conv_desc
             for (int rg = 0; rg < 4; ++rg) {
                 f32x4 v = {acc[g][rg * 4 + 0], acc[g][rg * 4 + 1], acc[g][rg * 4 + 2], acc[g][rg * 4 + 3]};
                 v = (v * unx) * unw;  // exact: powers of two
-                *reinterpret_cast<f32x4 *>(T + pr * 32 + (((rg * 2 + ph) ^ (pr & 7)) << 2)) = v;
+                a3d_turn_put(T, pr, rg * 2 + ph, v);
             }
             const int nl = g * 32 + qc * 4;
             f32x4 tv[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int qq = qr + 8 * j;
-                tv[j] = *reinterpret_cast<const f32x4 *>(T + qq * 32 + ((qc ^ (qq & 7)) << 2));
+                tv[j] = a3d_turn_get(T, qq, qc);
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -266,7 +239,7 @@ __global__ __launch_bounds__(256, 2) void conv_xs_b2b_kernel(const a3d_conv_desc
                 const int m = m0 + qq;
                 const f32x4 v = a3d_epilogue_math(d, tv[j], *reinterpret_cast<const f32x4 *>(ss + nl), *reinterpret_cast<const f32x4 *>(ss + BN + nl), true, rv[g][j]);
                 // (rows past M: zero inputs + the clamped residual row -- finite values nobody stores; a pixel's column of the second GEMM is its own)
-                *reinterpret_cast<f32x4 *>(T + qq * 32 + ((qc ^ (qq & 7)) << 2)) = v;
+                a3d_turn_put(T, qq, qc, v);
                 if (m < M) {
                     vmax[j] = fmaxf(vmax[j], a3d_absmax4(v));
                     *reinterpret_cast<f32x4 *>(d.y + (size_t)m * d.Cout + n0 + nl) = v;
@@ -275,13 +248,13 @@ __global__ __launch_bounds__(256, 2) void conv_xs_b2b_kernel(const a3d_conv_desc
             // second GEMM on the group's two 16-deep chunks: B fragment = 8 consecutive channels of the lane's pixel, split exactly three ways
 #pragma unroll
             for (int ci = 0; ci < 2; ++ci) {
-                bb_b16x8 yb[3];
+                bf16x8 yb[3];
                 {
-                    const f32x4 a0 = *reinterpret_cast<const f32x4 *>(T + pr * 32 + (((ci * 4 + ph * 2 + 0) ^ (pr & 7)) << 2));
-                    const f32x4 a1 = *reinterpret_cast<const f32x4 *>(T + pr * 32 + (((ci * 4 + ph * 2 + 1) ^ (pr & 7)) << 2));
-                    bb_b16x4 h0, m0_, l0, h1, m1_, l1;
-                    bb_split3(a0, h0, m0_, l0);
-                    bb_split3(a1, h1, m1_, l1);
+                    const f32x4 a0 = a3d_turn_get(T, pr, ci * 4 + ph * 2 + 0);
+                    const f32x4 a1 = a3d_turn_get(T, pr, ci * 4 + ph * 2 + 1);
+                    bf16x4 h0, m0_, l0, h1, m1_, l1;
+                    a3d_split3(a0, h0, m0_, l0);
+                    a3d_split3(a1, h1, m1_, l1);
                     yb[0] = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
                     yb[1] = __builtin_shufflevector(m0_, m1_, 0, 1, 2, 3, 4, 5, 6, 7);
                     yb[2] = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
@@ -289,11 +262,11 @@ __global__ __launch_bounds__(256, 2) void conv_xs_b2b_kernel(const a3d_conv_desc
 #pragma unroll
                 for (int tp = 0; tp < TP; ++tp) {
                     const unsigned char *st = enter(SPT + g * G2G + ci * TP + tp);
-                    bb_b16x8 fa[3][2];
+                    bf16x8 fa[3][2];
 #pragma unroll
                     for (int p = 0; p < 3; ++p)
 #pragma unroll
-                        for (int tl = 0; tl < 2; ++tl) fa[p][tl] = *reinterpret_cast<const bb_b16x8 *>(st + (p * 2 + tl) * 1024);
+                        for (int tl = 0; tl < 2; ++tl) fa[p][tl] = *reinterpret_cast<const bf16x8 *>(st + (p * 2 + tl) * 1024);
                     // conv_x3_kernel's six terms, in its order: (filter plane, activation plane) = (0,0) (0,1) (1,0) (1,1) (2,0) (0,2)
 #define BB_TERM(PA, PB)                                                                                                          \
     _Pragma("unroll") for (int tl = 0; tl < 2; ++tl) z[tp * 2 + tl] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[PA][tl], yb[PB], z[tp * 2 + tl], 0, 0, 0);
@@ -326,14 +299,14 @@ __global__ __launch_bounds__(256, 2) void conv_xs_b2b_kernel(const a3d_conv_desc
 #pragma unroll
         for (int rg = 0; rg < 4; ++rg) {
             const f32x4 v = {z[t][rg * 4 + 0], z[t][rg * 4 + 1], z[t][rg * 4 + 2], z[t][rg * 4 + 3]};
-            *reinterpret_cast<f32x4 *>(T + pr * 32 + (((rg * 2 + ph) ^ (pr & 7)) << 2)) = v;
+            a3d_turn_put(T, pr, rg * 2 + ph, v);
         }
         const int nl = t * 32 + qc * 4;
         f32x4 tv[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int qq = qr + 8 * j;
-            tv[j] = *reinterpret_cast<const f32x4 *>(T + qq * 32 + ((qc ^ (qq & 7)) << 2));
+            tv[j] = a3d_turn_get(T, qq, qc);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -345,26 +318,10 @@ __global__ __launch_bounds__(256, 2) void conv_xs_b2b_kernel(const a3d_conv_desc
             *reinterpret_cast<f32x4 *>(e.z + (size_t)m * Cout2 + nl) = v;
         }
     }
-    // maxima of both tensors, once per wave behind its last store (conv_xs_kernel)
-    auto note = [&](float *slot, const float (&vm)[4]) {
-        if (!slot) return;
-        if (one_image) {
-            a3d_note_amax(slot, m0 / hwo, fmaxf(fmaxf(vm[0], vm[1]), fmaxf(vm[2], vm[3])), true);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int m = m0 + qr + 8 * j;
-                float v = vm[j];
-                v = fmaxf(v, __shfl_xor(v, 1, 64));
-                v = fmaxf(v, __shfl_xor(v, 2, 64));
-                v = fmaxf(v, __shfl_xor(v, 4, 64));
-                a3d_note_amax(slot, m < M ? m / hwo : 0, v, m < M && qc == 0);
-            }
-        }
-    };
-    note(d.y_amax, vmax);
-    note(e.z_amax, zmax);
-    bb_wait_vm<0>();  // the DMAs issued past the last step must not land in the LDS of the next workgroup
+    // maxima of both tensors, once per wave behind its last store
+    a3d_note_rows(d.y_amax, vmax, one_image, m0, M, hwo, qr, qc);
+    a3d_note_rows(e.z_amax, zmax, one_image, m0, M, hwo, qr, qc);
+    a3d_wait_vm<0>();  // the DMAs issued past the last step must not land in the LDS of the next workgroup
 }
 template <int KC, int NG, int KS, int N2T, bool PREF>
 int launch_b2b(const a3d_conv_desc *d, const B2bArgs &e, hipStream_t s) {

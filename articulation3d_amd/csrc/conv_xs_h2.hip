@@ -17,23 +17,6 @@
 #include "conv_common.h"
 
 namespace {
-typedef _Float16 xs_h16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 xs_h16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t xs_rsrc(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
-// x * s = h + l (conv_bf16x3.hip split2h, element for element)
-__device__ __forceinline__ void xs_split(const f32x4 v, const float s, xs_h16x4 &h, xs_h16x4 &l) {
-    const f32x4 xs = v * s;
-    h = __builtin_convertvector(xs, xs_h16x4);
-    const f32x4 r = xs - __builtin_convertvector(h, f32x4);
-    l = __builtin_convertvector(r, xs_h16x4);
-}
-template <int N>
-__device__ __forceinline__ void xs_wait_vm() {
-    __asm__ volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 constexpr int XS_NST = 7;             // ring stages of 8 KiB
 constexpr int XS_D = XS_NST - 1;      // a stage's DMA is issued this many steps before its fragments are read
@@ -71,7 +54,7 @@ __global__ __launch_bounds__(256, 2) void conv_xs_kernel(const a3d_conv_desc d, 
     // ---- filter stream: w_x3 [Cin/16][2][Cout][16] fp16; piece (chunk c, plane p, rows n .. n+31) is 1 KiB contiguous.  A stage holds
     // pieces [chunk-in-stage][plane][group]; wave w moves pieces 2w and 2w+1.  Lane i lands at LDS byte 16 i of its piece = row i/2,
     // half i%2, and fetches the k half the image keeps there: half ^ ((row >> 3) & 1)  (the layout conv_x3_kernel reads).
-    const __amdgpu_buffer_rsrc_t rw = xs_rsrc(d.w_x3, (unsigned)((size_t)KC * d.Cout * 64));
+    const __amdgpu_buffer_rsrc_t rw = a3d_rsrc(d.w_x3, (unsigned)((size_t)KC * d.Cout * 64));
     const int wvoff = (lane >> 1) * 32 + (((lane & 1) ^ ((lane >> 4) & 1)) << 4);
     const int uw = __builtin_amdgcn_readfirstlane(wave);
     int dma_q = 0, dma_st = 0, rd_st = 0;  // next step to fetch; ring stage it goes to; ring stage the next fragment reads come from
@@ -87,8 +70,7 @@ __global__ __launch_bounds__(256, 2) void conv_xs_kernel(const a3d_conv_desc d, 
             const int kl = j / (2 * NG), p = (j / NG) & 1, g = j % NG;
             const int c = t * KS + kl;
             const int soff = q < Q ? ((c * 2 + p) * d.Cout + nbeg + ns * BN + g * 32) * 32 : 0;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void *)(st + j * 1024), 16, voff,
-                                                     __builtin_amdgcn_readfirstlane(soff), 0, 0);
+            a3d_dma16(rw, st + j * 1024, voff, __builtin_amdgcn_readfirstlane(soff));
         }
     };
 #pragma unroll
@@ -98,22 +80,22 @@ __global__ __launch_bounds__(256, 2) void conv_xs_kernel(const a3d_conv_desc d, 
     const int mp = m0 + (lane & 31);
     const bool mok = mp < M;
     const float sx = mok ? a3d_in_scale(d, mp / hwo) : 1.f;
-    xs_h16x8 xh[KC], xl[KC];
+    h16x8 xh[KC], xl[KC];
     {
-        const __amdgpu_buffer_rsrc_t rx = xs_rsrc(d.x, (unsigned)((size_t)M * d.Cin * 4));
+        const __amdgpu_buffer_rsrc_t rx = a3d_rsrc(d.x, (unsigned)((size_t)M * d.Cin * 4));
         const int voff = mok ? (mp * d.Cin + (lane >> 5) * 8) * 4 : -1;
         f32x4 raw[KC][2];
 #pragma unroll
         for (int c = 0; c < KC; ++c) {
-            raw[c][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, voff, c * 64, 0));
-            raw[c][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, voff, c * 64 + 16, 0));
+            raw[c][0] = a3d_load4(rx, voff, c * 64);
+            raw[c][1] = a3d_load4(rx, voff, c * 64 + 16);
         }
-        xs_wait_vm<0>();
+        a3d_wait_vm<0>();
 #pragma unroll
         for (int c = 0; c < KC; ++c) {
-            xs_h16x4 h0, l0, h1, l1;
-            xs_split(raw[c][0], sx, h0, l0);
-            xs_split(raw[c][1], sx, h1, l1);
+            h16x4 h0, l0, h1, l1;
+            a3d_split2h(raw[c][0], sx, h0, l0);
+            a3d_split2h(raw[c][1], sx, h1, l1);
             xh[c] = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
             xl[c] = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
         }
@@ -157,8 +139,8 @@ __global__ __launch_bounds__(256, 2) void conv_xs_kernel(const a3d_conv_desc d, 
         for (int t = 0; t < SPT; ++t, ++q) {
             // the DMA of step q (issued XS_D steps ago) has landed: younger than it are the DMAs of the XS_D - 1 steps since and,
             // during the first XS_D steps of an N step, that step's residual loads (loads retire in order)
-            if (has_res && t < XS_D) xs_wait_vm<2 * (XS_D - 1) + R>();
-            else xs_wait_vm<2 * (XS_D - 1)>();
+            if (has_res && t < XS_D) a3d_wait_vm<2 * (XS_D - 1) + R>();
+            else a3d_wait_vm<2 * (XS_D - 1)>();
             // (a bare barrier: __syncthreads() carries a workgroup fence, and the compiler completes every LDS-DMA in flight in front
             // of a fence -- vmcnt(0) -- which would put the whole ring's latency back into every step)
             __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -169,11 +151,11 @@ __global__ __launch_bounds__(256, 2) void conv_xs_kernel(const a3d_conv_desc d, 
 #pragma unroll
             for (int kl = 0; kl < KS; ++kl) {
                 const int c = t * KS + kl;
-                xs_h16x8 fa[2][NG];
+                h16x8 fa[2][NG];
 #pragma unroll
                 for (int p = 0; p < 2; ++p)
 #pragma unroll
-                    for (int g = 0; g < NG; ++g) fa[p][g] = *reinterpret_cast<const xs_h16x8 *>(st + ((kl * 2 + p) * NG + g) * 1024);
+                    for (int g = 0; g < NG; ++g) fa[p][g] = *reinterpret_cast<const h16x8 *>(st + ((kl * 2 + p) * NG + g) * 1024);
 #pragma unroll
                 for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[0][g], xh[c], acc[g], 0, 0, 0);
 #pragma unroll
@@ -182,10 +164,10 @@ __global__ __launch_bounds__(256, 2) void conv_xs_kernel(const a3d_conv_desc d, 
                 for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[1][g], xh[c], acc[g], 0, 0, 0);
             }
         }
-        // ---- epilogue of the N step (conv_x3_kernel's row-major form: a 32 x 32 tile goes through 4 KiB of LDS, XOR-swizzled)
+        // ---- epilogue of the N step: each 32 x 32 tile comes back row-major through T (a3d_turn_put / a3d_turn_get)
         if (has_res) {  // the residual loads are older than the DMAs of the last min(SPT, XS_D) steps
-            if constexpr (SPT < XS_D) xs_wait_vm<2 * SPT>();
-            else xs_wait_vm<2 * XS_D>();
+            if constexpr (SPT < XS_D) a3d_wait_vm<2 * SPT>();
+            else a3d_wait_vm<2 * XS_D>();
         }
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
@@ -193,14 +175,14 @@ __global__ __launch_bounds__(256, 2) void conv_xs_kernel(const a3d_conv_desc d, 
             for (int rg = 0; rg < 4; ++rg) {
                 f32x4 v = {acc[g][rg * 4 + 0], acc[g][rg * 4 + 1], acc[g][rg * 4 + 2], acc[g][rg * 4 + 3]};
                 v = (v * unx) * unw;  // exact: powers of two
-                *reinterpret_cast<f32x4 *>(T + pr * 32 + (((rg * 2 + ph) ^ (pr & 7)) << 2)) = v;
+                a3d_turn_put(T, pr, rg * 2 + ph, v);
             }
             const int nl = g * 32 + qc * 4;
             f32x4 tv[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int qq = qr + 8 * j;
-                tv[j] = *reinterpret_cast<const f32x4 *>(T + qq * 32 + ((qc ^ (qq & 7)) << 2));
+                tv[j] = a3d_turn_get(T, qq, qc);
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -212,9 +194,7 @@ __global__ __launch_bounds__(256, 2) void conv_xs_kernel(const a3d_conv_desc d, 
             }
         }
     }
-    // The maxima go out ONCE per wave, behind its last store: an atomic on an image's slot queues behind every other workgroup's at the
-    // L2, and a wave that goes on to another N step would wait for it at its next counted vmcnt (measured: 0.97 -> 0.43 ms on the
-    // res2 64 -> 256 layer).
+    // a3d_note_rows, spelled out: behind the helper the three instantiations' row index was computed with its operands swapped
     if (d.y_amax) {
         if (one_image) {
             a3d_note_amax(d.y_amax, m0 / hwo, fmaxf(fmaxf(vmax[0], vmax[1]), fmaxf(vmax[2], vmax[3])), true);
@@ -222,15 +202,12 @@ __global__ __launch_bounds__(256, 2) void conv_xs_kernel(const a3d_conv_desc d, 
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int m = m0 + qr + 8 * j;
-                float v = vmax[j];
-                v = fmaxf(v, __shfl_xor(v, 1, 64));
-                v = fmaxf(v, __shfl_xor(v, 2, 64));
-                v = fmaxf(v, __shfl_xor(v, 4, 64));
+                const float v = a3d_max8(vmax[j]);
                 a3d_note_amax(d.y_amax, m < M ? m / hwo : 0, v, m < M && qc == 0);
             }
         }
     }
-    xs_wait_vm<0>();  // the DMAs issued past the last step must not land in the LDS of the next workgroup
+    a3d_wait_vm<0>();  // the DMAs issued past the last step must not land in the LDS of the next workgroup
 }
 
 template <int KC, int NG, int KS>

@@ -113,8 +113,6 @@ __global__ __launch_bounds__(256) void roi_order_kernel(const float *boxes, cons
 // and then splits and stores the row -- the same bytes as the fp32 row (2 + 2 per element), the bits fc1's loader computed from it.
 // NW waves per workgroup: 7 for the 7x7 pooler (wave w pools column w of every bin row: the waves of a workgroup stay neighbours in
 // the pyramid, and 49 bins are 7 rounds with no idle wave), 4 otherwise.
-typedef _Float16 ra_h16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 ra_h16x8 __attribute__((ext_vector_type(8)));
 template <int NW, bool H2, bool ROLL = false>
 __global__ __launch_bounds__(64 * NW, H2 ? 3 : 1) void roi_align_fpn_kernel(const RoiArgs a) {
     extern __shared__ __attribute__((aligned(16))) float pooled_lds[];  // H2: [P*P][C]
@@ -422,7 +420,7 @@ __global__ __launch_bounds__(64 * NW, H2 ? 3 : 1) void roi_align_fpn_kernel(cons
             }
         }
         if constexpr (H2) {
-            // x * s = h + l, s = the scale fc1 derives from out_amax[row] (a3d_in_scale): conv_bf16x3_wide.hip's wx_split2h on 8 channels
+            // x * s = h + l, s = the scale fc1 derives from out_amax[row] (a3d_in_scale): a3d_split2h on 8 channels
             // per thread = one 16-byte half of a chunk's h row and of its l row
             const float sc = a3d_pow2_scale(m);
             unsigned char *hrow = a.out_h2 + (size_t)row * a.P * a.P * a.C * 4;
@@ -430,13 +428,12 @@ __global__ __launch_bounds__(64 * NW, H2 ? 3 : 1) void roi_align_fpn_kernel(cons
             for (int i = threadIdx.x; i < n8; i += 64 * NW) {
                 const f32x4 v0 = *reinterpret_cast<const f32x4 *>(pooled_lds + (size_t)i * 8);
                 const f32x4 v1 = *reinterpret_cast<const f32x4 *>(pooled_lds + (size_t)i * 8 + 4);
-                const f32x4 x0 = v0 * sc, x1 = v1 * sc;
-                const ra_h16x4 h0 = __builtin_convertvector(x0, ra_h16x4), h1 = __builtin_convertvector(x1, ra_h16x4);
-                const ra_h16x4 l0 = __builtin_convertvector(x0 - __builtin_convertvector(h0, f32x4), ra_h16x4);
-                const ra_h16x4 l1 = __builtin_convertvector(x1 - __builtin_convertvector(h1, f32x4), ra_h16x4);
+                h16x4 h0, l0, h1, l1;
+                a3d_split2h(v0, sc, h0, l0);
+                a3d_split2h(v1, sc, h1, l1);
                 unsigned char *dst = hrow + (size_t)(i >> 1) * 64 + (i & 1) * 16;
-                *reinterpret_cast<ra_h16x8 *>(dst) = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-                *reinterpret_cast<ra_h16x8 *>(dst + 32) = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
+                *reinterpret_cast<h16x8 *>(dst) = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
+                *reinterpret_cast<h16x8 *>(dst + 32) = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
             }
         }
     }

@@ -6,7 +6,7 @@
 //
 // All of these are HBM-bound element / row kernels; built with -ffp-contract=off so IoU and delta arithmetic round like
 // the reference's separate mul/add/div (the matcher's labels are compared bit-exactly).
-#include "a3d_common.h"
+#include "conv_prims.h"
 #include "../../include/a3d.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -591,11 +591,10 @@ extern "C" int a3d_box_loss(const a3d_box_loss_desc *d, void *stream) {
 template <bool GB16>  // GB16: the gradient arrives as bf16 (the all-reduced payload itself: no widening pass over the flat buffer)
 __global__ void sgd_kernel(float *__restrict__ p, const void *__restrict__ g, float *__restrict__ buf, size_t n4, float lr, float momentum,
                            float wd, float grad_scale, int first) {
-    typedef __bf16 b4 __attribute__((ext_vector_type(4)));
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         f32x4 pv = reinterpret_cast<f32x4 *>(p)[i];
         f32x4 gv;
-        if constexpr (GB16) gv = __builtin_convertvector(reinterpret_cast<const b4 *>(g)[i], f32x4);
+        if constexpr (GB16) gv = __builtin_convertvector(reinterpret_cast<const bf16x4 *>(g)[i], f32x4);
         else gv = reinterpret_cast<const f32x4 *>(g)[i];
         const f32x4 dv = grad_scale * gv + wd * pv;
         f32x4 bv = first ? dv : momentum * reinterpret_cast<f32x4 *>(buf)[i] + dv;
@@ -633,16 +632,14 @@ extern "C" int a3d_sgd_momentum_bf16g(float *p, const void *g_bf16, float *buf, 
 // torch's DDP bf16_compress_hook: the gradient is divided by the world size, rounded to bf16 (nearest even), summed by the collective
 // in bf16 and widened back.  Two HBM-bound passes over the flat gradient buffer; the collective moves half the bytes (82 MB, not 164).
 __global__ __launch_bounds__(256) void f32_to_bf16_scaled_kernel(const float *__restrict__ src, __bf16 *__restrict__ dst, size_t n4, float scale) {
-    typedef __bf16 b4 __attribute__((ext_vector_type(4)));
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         const f32x4 v = reinterpret_cast<const f32x4 *>(src)[i] * scale;
-        reinterpret_cast<b4 *>(dst)[i] = __builtin_convertvector(v, b4);
+        reinterpret_cast<bf16x4 *>(dst)[i] = __builtin_convertvector(v, bf16x4);
     }
 }
 __global__ __launch_bounds__(256) void bf16_to_f32_kernel(const __bf16 *__restrict__ src, float *__restrict__ dst, size_t n4) {
-    typedef __bf16 b4 __attribute__((ext_vector_type(4)));
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x)
-        reinterpret_cast<f32x4 *>(dst)[i] = __builtin_convertvector(reinterpret_cast<const b4 *>(src)[i], f32x4);
+        reinterpret_cast<f32x4 *>(dst)[i] = __builtin_convertvector(reinterpret_cast<const bf16x4 *>(src)[i], f32x4);
 }
 
 extern "C" int a3d_f32_to_bf16_scaled(const float *src, void *dst, size_t n, float scale, void *stream) {

@@ -16,7 +16,7 @@
 //   * 512 threads, one workgroup per CU, the two halves of the workgroup in ANTIPHASE (waves 4-7 run half a chunk behind waves 0-3;
 //     the wave pairs of a SIMD alternate a memory phase -- fragment reads, DMA issue, the split's vector work -- with a compute phase
 //     of 12 TM MFMAs back to back).  conv_wino.hip's ping-pong loop describes the barrier protocol; it is the same here.
-// Per output element the operations are conv_x3_kernel's (split2h, 16-deep steps in k order, h.h + h.l + l.h per step into one fp32
+// Per output element the operations are conv_x3_kernel's (a3d_split2h, 16-deep steps in k order, h.h + h.l + l.h per step into one fp32
 // accumulator, the shared epilogue): the kernels agree BIT FOR BIT (tests/test_gpu_parity.py), so the launcher may choose by size.
 #include "conv_common.h"
 
