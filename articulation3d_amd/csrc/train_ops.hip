@@ -498,19 +498,29 @@ extern "C" size_t a3d_loss_workspace_bytes(void) { return (size_t)5 * A3D_LOSS_B
 extern "C" int a3d_rpn_loss(const a3d_rpn_loss_desc *d, void *stream) {
     if (!d || !d->labels || !d->matched_idx || !d->gt_boxes || !d->loss || !d->workspace) return A3D_ERR_ARG;
     if (d->B <= 0 || d->L < 1 || d->L > 5 || d->A < 1 || d->A > 3 || d->CH < 5 * d->A || !(d->normalizer > 0.f)) return A3D_ERR_ARG;
+    // everything is checked before the first launch: a refused descriptor has written no byte.  (The level loop used to launch as it
+    // went and compared the levels' sum with Atotal afterwards: a misdeclared Atotal ran every level on the wrong label pitch first.)
+    int blocks[5];
+    long long off_ll = 0;
+    int nparts = 0;
+    for (int l = 0; l < d->L; ++l) {
+        if (!d->head[l] || !d->dhead[l] || d->Hf[l] <= 0 || d->Wf[l] <= 0) return A3D_ERR_ARG;
+        const long long total = (long long)d->B * d->Hf[l] * d->Wf[l];
+        if (total * d->A > 0x7fffffffLL) return A3D_ERR_ARG;  // (the kernel indexes cells and anchors in int)
+        blocks[l] = total > (long long)A3D_LOSS_BLOCKS * 256 ? A3D_LOSS_BLOCKS : (int)((total + 255) / 256);
+        off_ll += (long long)d->Hf[l] * d->Wf[l] * d->A;
+        nparts += blocks[l];
+    }
+    if (off_ll != (long long)d->Atotal) return A3D_ERR_ARG;
+    if ((size_t)nparts * 2 * sizeof(float) > a3d_loss_workspace_bytes()) return A3D_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     a3d_begin();
-    int off = 0, nparts = 0;
+    int off = 0, part = 0;
     for (int l = 0; l < d->L; ++l) {
-        if (!d->head[l] || !d->dhead[l]) return A3D_ERR_ARG;
-        const int total = d->B * d->Hf[l] * d->Wf[l];
-        int blocks = (total + 255) / 256;
-        if (blocks > A3D_LOSS_BLOCKS) blocks = A3D_LOSS_BLOCKS;
-        hipLaunchKernelGGL(rpn_loss_kernel, dim3(blocks), dim3(256), 0, s, *d, l, off, d->workspace, nparts);
+        hipLaunchKernelGGL(rpn_loss_kernel, dim3(blocks[l]), dim3(256), 0, s, *d, l, off, d->workspace, part);
         off += d->Hf[l] * d->Wf[l] * d->A;
-        nparts += blocks;
+        part += blocks[l];
     }
-    if (off != d->Atotal) return A3D_ERR_ARG;
     hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(64), 0, s, d->workspace, nparts, 2, 1.0f / d->normalizer, d->loss);
     return a3d_check_launch();
 }

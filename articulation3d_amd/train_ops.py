@@ -284,14 +284,17 @@ def match_boxes(boxes: torch.Tensor, gt_boxes: torch.Tensor, gt_count: torch.Ten
 
 
 def rpn_loss(heads: Sequence[torch.Tensor], strides: Sequence[int], cell_anchors: torch.Tensor, labels: torch.Tensor,
-             matched_idx: torch.Tensor, gt_boxes: torch.Tensor, *, A: int, weights, normalizer: float):
-    """heads[l] [B,Hf,Wf,CH] -> (loss [2] = (loss_rpn_cls, loss_rpn_loc), dheads list of the same shapes)."""
+             matched_idx: torch.Tensor, gt_boxes: torch.Tensor, *, A: int, weights, normalizer: float,
+             out: Optional[tuple] = None):
+    """heads[l] [B,Hf,Wf,CH] -> (loss [2] = (loss_rpn_cls, loss_rpn_loc), dheads list of the same shapes).
+    out: preallocated (loss, dheads) to write into instead (a refused descriptor leaves them untouched)."""
     d = _lib.RpnLossDesc()
     dheads = []
     ca = cell_anchors.detach().cpu().float()
     for l, h in enumerate(heads):
         _req(h)
-        g = torch.empty_like(h)
+        g = torch.empty_like(h) if out is None else _req(out[1][l])
+        assert g.shape == h.shape
         dheads.append(g)
         d.head[l], d.dhead[l], d.Hf[l], d.Wf[l], d.stride[l] = h.data_ptr(), g.data_ptr(), h.shape[1], h.shape[2], int(strides[l])
         for a in range(A):
@@ -304,7 +307,7 @@ def rpn_loss(heads: Sequence[torch.Tensor], strides: Sequence[int], cell_anchors
         d.weights[k] = float(weights[k])
     d.normalizer = float(normalizer)
     ws = torch.empty(_lib.lib().a3d_loss_workspace_bytes() // 4, device=labels.device, dtype=torch.float32)
-    loss = torch.empty(2, device=labels.device, dtype=torch.float32)
+    loss = torch.empty(2, device=labels.device, dtype=torch.float32) if out is None else _req(out[0])
     d.workspace, d.loss = ws.data_ptr(), loss.data_ptr()
     _lib.check(_lib.lib().a3d_rpn_loss(C.byref(d), _stream()), "a3d_rpn_loss")
     return loss, dheads

@@ -151,7 +151,7 @@ def rpn_losses(logits: List[torch.Tensor], deltas: List[torch.Tensor], anchors, 
     tgt = torch.stack([get_deltas(anchors, matched_gt[n], cfg.rpn_weights) for n in range(N)])
     loc = (dl[pos] - tgt[pos]).abs().sum()  # smooth_l1 with beta = 0
     valid = labels >= 0
-    obj = F.binary_cross_entropy_with_logits(lg[valid], labels[valid].float(), reduction="sum")
+    obj = F.binary_cross_entropy_with_logits(lg[valid], labels[valid].to(lg.dtype), reduction="sum")  # (targets in the logits' dtype: float64 logits stay float64)
     norm = tc.rpn_batch_per_image * N
     return {"loss_rpn_cls": obj / norm, "loss_rpn_loc": loc / norm}
 
