@@ -135,6 +135,22 @@ class AxisLossDesc(C.Structure):
     ]
 
 
+class MaskTargetsDesc(C.Structure):
+    _fields_ = [
+        ("masks", fptr), ("boxes", fptr), ("count", fptr), ("row_offset", fptr), ("row_gt", fptr), ("live", fptr), ("targets", fptr),
+        ("B", C.c_int), ("max_gt", C.c_int), ("H", C.c_int), ("W", C.c_int), ("cap", C.c_int), ("rows", C.c_int), ("S", C.c_int),
+        ("pad_", C.c_int),
+    ]
+
+
+class MaskLossDesc(C.Structure):
+    _fields_ = [
+        ("yu", fptr), ("targets", fptr), ("w", fptr), ("b", fptr), ("live", fptr), ("dyu", fptr), ("z", fptr), ("out", fptr),
+        ("workspace", fptr),
+        ("rows", C.c_int), ("P", C.c_int), ("C", C.c_int), ("pad_", C.c_int),
+    ]
+
+
 class TransposeItem(C.Structure):
     _fields_ = [("w", fptr), ("scale", fptr), ("wt", fptr), ("Cout", C.c_int), ("KH", C.c_int), ("KW", C.c_int), ("Cin", C.c_int),
                 ("block0", C.c_int), ("pad_", C.c_int)]
@@ -261,6 +277,9 @@ SIGNATURES = {
     "a3d_colsum_bf16": (C.c_int, [fptr, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr]),
     "a3d_colsum_rows": (C.c_int, [fptr, C.c_int, fptr, fptr, C.c_int, fptr, C.c_int, C.c_int, fptr]),
     "a3d_axis_loss": (C.c_int, [C.POINTER(AxisLossDesc), fptr]),
+    "a3d_mask_targets": (C.c_int, [C.POINTER(MaskTargetsDesc), fptr]),
+    "a3d_mask_loss_workspace_bytes": (C.c_size_t, []),
+    "a3d_mask_loss": (C.c_int, [C.POINTER(MaskLossDesc), fptr]),
     "a3d_roi_align_fpn_backward": (C.c_int, [C.POINTER(RoiAlignBwdDesc), fptr]),
     "a3d_roi_align_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(RoiAlignBwdDesc)]),
     "a3d_roi_align_fpn_backward_gather": (C.c_int, [C.POINTER(RoiAlignBwdDesc), fptr, fptr]),
@@ -283,7 +302,7 @@ SIGNATURES = {
 
 STRUCT_IDS = {0: ConvDesc, 1: RpnDesc, 2: BoxDetDesc, 3: RoiAlignDesc, 4: PasteDesc, 5: PackDesc, 6: WgradDesc,
               7: RoiAlignBwdDesc, 8: MatchDesc, 9: RpnLossDesc, 10: BoxLossDesc, 11: RoiSampleDesc, 12: SweepDesc, 13: TransposeItem,
-              14: AxisLossDesc}
+              14: AxisLossDesc, 15: MaskTargetsDesc, 16: MaskLossDesc}
 
 _lib = None
 

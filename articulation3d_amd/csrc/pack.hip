@@ -188,6 +188,8 @@ extern "C" size_t a3d_struct_size(int id) {
         case 12: return sizeof(a3d_sweep_desc);
         case 13: return sizeof(a3d_transpose_item);
         case 14: return sizeof(a3d_axis_loss_desc);
+        case 15: return sizeof(a3d_mask_targets_desc);
+        case 16: return sizeof(a3d_mask_loss_desc);
         default: return 0;
     }
 }

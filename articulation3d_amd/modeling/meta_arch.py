@@ -23,7 +23,7 @@ from torch import nn
 from .. import ops
 from ..registry import META_ARCH_REGISTRY
 from ..streams import SMALL_BATCH
-from ..structures import Boxes, ImageList, Instances
+from ..structures import Boxes, ImageList, Instances, gt_bitmasks
 from .backbone import build_backbone
 from .depth_head import build_depth_head
 from .layers import to_nchw_view
@@ -34,6 +34,9 @@ from .rpn import build_proposal_generator
 __all__ = ["PlaneRCNN", "BatchedOutput", "build_model"]
 
 POST_SCORE_THRESH = 0.1  # planercnn.py:217
+# training stage 3 (the mask share of config/step3_plane.yaml): the head that trains, and the heads that must be off or in MODEL.FREEZE
+STAGE3_TRAINABLE = "roi_heads.mask_head"
+STAGE3_FROZEN_HEADS = ("roi_heads.plane_head", "roi_heads.axis_head", "depth_head")
 
 
 @dataclass
@@ -266,26 +269,40 @@ class PlaneRCNN(nn.Module):
     STAGE2_FREEZE = ("backbone", "proposal_generator", "roi_heads.box_head", "roi_heads.box_predictor")
 
     def training_stage(self) -> int:
-        """Which of the reference's training stages this model's configuration is: 1 (config/step1_bbox.yaml: box branch only) or
-        2 (config/step2_axis.yaml: AXIS_ON, MASK / PLANE / DEPTH off, FREEZE covering the four detector modules).  Anything else
-        (step3_plane.yaml's mask / plane / depth losses among it) raises NotImplementedError."""
+        """Which training stage this model's configuration is: 1 (config/step1_bbox.yaml: box branch only), 2 (config/step2_axis.yaml:
+        AXIS_ON, MASK / PLANE / DEPTH off, FREEZE covering the four detector modules) or 3, the MASK SHARE of config/step3_plane.yaml
+        (configs/step3_mask.yaml: MASK_ON with roi_heads.mask_head trainable, FREEZE covering the four detector modules, and each of the
+        plane, axis and depth heads either off or frozen -- the reference skips a frozen head in training the same way).  Anything else
+        (step3_plane.yaml's own flags, whose plane and depth losses have no training path, among it) raises NotImplementedError."""
         rh = self.roi_heads
-        others = self.depth_head_on or getattr(rh, "mask_on", False) or getattr(rh, "plane_on", False)
-        axis = getattr(rh, "axis_on", False)
+        mask, plane, axis = (bool(getattr(rh, n, False)) for n in ("mask_on", "plane_on", "axis_on"))
+        others = self.depth_head_on or mask or plane
+        frozen = set(self._freeze)
         if not others and not axis:
             return 1
-        if not others and axis and set(self.STAGE2_FREEZE) <= set(self._freeze):
+        if not others and axis and set(self.STAGE2_FREEZE) <= frozen:
             return 2
-        raise NotImplementedError("training is implemented for config/step1_bbox.yaml (MASK_ON / PLANE_ON / AXIS_ON / DEPTH_ON false) and "
+        on = {"roi_heads.plane_head": plane, "roi_heads.axis_head": axis, "depth_head": bool(self.depth_head_on)}
+        if (mask and STAGE3_TRAINABLE not in frozen and set(self.STAGE2_FREEZE) <= frozen
+                and all(not on[h] or h in frozen for h in STAGE3_FROZEN_HEADS)):
+            return 3
+        raise NotImplementedError("training is implemented for config/step1_bbox.yaml (MASK_ON / PLANE_ON / AXIS_ON / DEPTH_ON false), "
                                   "config/step2_axis.yaml (AXIS_ON true, MASK_ON / PLANE_ON / DEPTH_ON false, FREEZE: " + str(list(self.STAGE2_FREEZE)) +
-                                  "); the mask, plane and depth losses of step3_plane.yaml are out of scope")
+                                  ") and the mask share of step3_plane.yaml (configs/step3_mask.yaml: MASK_ON true, " + STAGE3_TRAINABLE +
+                                  " trainable, FREEZE covering the detector and every other head that is on: " + str(list(STAGE3_FROZEN_HEADS)) +
+                                  "); the plane and depth losses of step3_plane.yaml are out of scope")
 
     def trainer(self, solver=None, precision: str = "bf16x3"):
         """The hand-written training step behind the reference's training-mode call: created on first use (it copies every
         trainable parameter into its flat buffer).  `articulation3d_amd.engine.build_optimizer` returns the optimiser bound to it.
-        Stage 1: DetectorTrainer; stage 2: training_axis.AxisTrainer (see training_stage)."""
+        Stage 1: DetectorTrainer; stage 2: training_axis.AxisTrainer; stage 3: training_mask.MaskTrainer (see training_stage)."""
         if getattr(self, "_trainer", None) is None:
-            if self.training_stage() == 2:
+            stage = self.training_stage()
+            if stage == 3:
+                from ..training_mask import MaskTrainer
+
+                self._trainer = MaskTrainer(self, solver, precision=precision)
+            elif stage == 2:
                 from ..training_axis import AxisTrainer
 
                 self._trainer = AxisTrainer(self, solver, precision=precision)
@@ -298,7 +315,8 @@ class PlaneRCNN(nn.Module):
     def training_forward(self, batched_inputs):
         """`model(batched_inputs)` in training mode, as detectron2's SimpleTrainer.run_step calls it (tools/train_net.py:84-104 ->
         planercnn.py:83-123): list of {"image": CHW uint8 BGR, "instances": Instances(gt_boxes, gt_classes)} -> the loss dict
-        {loss_cls, loss_box_reg, loss_rpn_cls, loss_rpn_loc}.  There is no autograd graph: the call runs forward AND backward
+        {loss_cls, loss_box_reg, loss_rpn_cls, loss_rpn_loc} (stage 2: + the axis losses; stage 3: Instances carry gt_masks, a
+        structures.BitMasks or a [G,H,W] tensor, and the dict is {loss_cls, loss_box_reg, loss_mask}).  There is no autograd graph: the call runs forward AND backward
         (DetectorTrainer.forward_backward) and leaves the gradients of the summed loss in the trainer's flat buffer; the returned
         scalars accept `.backward()` so the reference's loop body stays as it is, and `engine.build_optimizer(cfg, model).step()`
         applies the fused all-reduce + SGD launch.  Only the step1_bbox configuration (BASELINE configs[4]: box branch; mask /
@@ -312,8 +330,12 @@ class PlaneRCNN(nn.Module):
             frames = frames.round().clamp(0, 255).to(torch.uint8)  # (detectron2's mapper hands over uint8; tolerate float 0-255)
         gt_boxes = [x["instances"].gt_boxes.tensor.float() for x in batched_inputs]
         gt_classes = [x["instances"].gt_classes.long() for x in batched_inputs]
+        if stage == 3:  # (polygon ground truth is refused before anything is built or run: NotImplementedError)
+            masks = [gt_bitmasks(x["instances"].gt_masks) for x in batched_inputs]
         tr = self.trainer()
-        if stage == 2:  # step2_axis.yaml: {loss_cls, loss_box_reg} of the frozen detector + {loss_rot_axis, loss_tran_axis}
+        if stage == 3:  # configs/step3_mask.yaml: {loss_cls, loss_box_reg} of the frozen detector + loss_mask
+            losses, _aux = tr.forward_backward(frames, gt_boxes, gt_classes, masks, exchange=True)
+        elif stage == 2:  # step2_axis.yaml: {loss_cls, loss_box_reg} of the frozen detector + {loss_rot_axis, loss_tran_axis}
             rot = [x["instances"].gt_rot_axis.float() for x in batched_inputs]
             tran = [x["instances"].gt_tran_axis.float() for x in batched_inputs]
             losses, _aux = tr.forward_backward(frames, gt_boxes, gt_classes, rot, tran, exchange=True)
@@ -326,7 +348,7 @@ class PlaneRCNN(nn.Module):
     def train(self, mode: bool = True):
         """Leaving training mode writes the trainer's parameters back into the modules (inference packs its weights from them)."""
         if not mode and getattr(self, "_trainer", None) is not None and self.training:
-            self.load_state_dict(self._trainer.export_state_dict(), strict=False)  # (stage 2: the axis head's entries only)
+            self.load_state_dict(self._trainer.export_state_dict(), strict=False)  # (stage 2 / 3: the axis / mask head's entries only)
         return super().train(mode)
 
     # batches up to this size run the depth decoder on a second HIP stream beside the ROI branch (0 disables: every kernel then runs alone)

@@ -102,6 +102,57 @@ class Boxes:
         yield from self.tensor
 
 
+class BitMasks:
+    """N x H x W ground-truth masks of one image at image resolution, one bit per pixel (detectron2's BitMasks, INPUT.MASK_FORMAT:
+    bitmask).  Minimal: what the mask head's training step reads (`.tensor`, len, indexing, `to`).  The crop to each proposal box
+    (crop_and_resize) is the a3d_mask_targets kernel, not a method."""
+
+    def __init__(self, tensor):
+        if not isinstance(tensor, torch.Tensor):
+            tensor = torch.as_tensor(np.asarray(tensor))
+        assert tensor.dtype in (torch.bool, torch.uint8), f"BitMasks holds bool or uint8, got {tensor.dtype}"
+        assert tensor.dim() == 3, tensor.size()
+        self.tensor = tensor
+        self.image_size = tuple(tensor.shape[1:])
+
+    def to(self, device):
+        return BitMasks(to_host(self.tensor) if _is_cpu(device) else self.tensor.to(device=device))
+
+    def __getitem__(self, item):
+        if isinstance(item, int):
+            return BitMasks(self.tensor[item][None])
+        m = self.tensor[item]
+        assert m.dim() == 3
+        return BitMasks(m)
+
+    def __len__(self):
+        return self.tensor.shape[0]
+
+    def __repr__(self):
+        return f"BitMasks(num_instances={len(self)}, image_size={self.image_size})"
+
+    @property
+    def device(self):
+        return self.tensor.device
+
+
+POLYGON_MASKS_MESSAGE = (
+    "gt_masks carries .polygons: polygon ground truth is out of scope; use INPUT.MASK_FORMAT: bitmask (structures.BitMasks or a "
+    "[G, H, W] bool / uint8 tensor).  For polygons detectron2 rasterises each polygon INSIDE each proposal box with pycocotools, "
+    "whose result this package cannot restate or check")
+
+
+def gt_bitmasks(gt_masks) -> torch.Tensor:
+    """The [G, H, W] tensor of an image's ground-truth masks: a BitMasks or a bare bool / uint8 tensor.  Anything carrying `.polygons`
+    (detectron2's PolygonMasks, INPUT.MASK_FORMAT: polygon) raises NotImplementedError."""
+    if hasattr(gt_masks, "polygons"):
+        raise NotImplementedError(POLYGON_MASKS_MESSAGE)
+    t = gt_masks.tensor if hasattr(gt_masks, "tensor") else gt_masks
+    if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype not in (torch.bool, torch.uint8):
+        raise TypeError("gt_masks: a structures.BitMasks or a [G, H, W] bool / uint8 tensor")
+    return t
+
+
 class Instances:
     """Per-image bag of equally long fields, detectron2-style (set by attribute)."""
 

@@ -237,6 +237,56 @@ def axis_loss(raw_rot: torch.Tensor, raw_tran: torch.Tensor, live: torch.Tensor,
     return loss, d_rot, d_tran
 
 
+def mask_targets(masks: torch.Tensor, boxes: torch.Tensor, count: torch.Tensor, row_offset: torch.Tensor, row_gt: torch.Tensor,
+                 live: torch.Tensor, *, rows: int, size: int = 28, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The mask targets of the live compact rows (a3d_mask_targets): masks [B, max_gt, H, W] uint8, boxes [B, cap, 4], count [B],
+    row_offset [B+1], row_gt [rows], live: device int32 -> uint8 [rows, size, size] (0 / 1; rows past *live are left as they are)."""
+    B, G, H, W = _req(masks, torch.uint8).shape
+    assert tuple(_req(boxes).shape[::2]) == (B, 4) and boxes.dim() == 3
+    assert _req(count, torch.int32).numel() == B and _req(row_offset, torch.int32).numel() == B + 1
+    assert _req(row_gt, torch.int32).numel() >= rows
+    if out is None:
+        out = torch.empty((rows, size, size), device=masks.device, dtype=torch.uint8)
+    assert tuple(_req(out, torch.uint8).shape) == (rows, size, size)
+    d = _lib.MaskTargetsDesc()
+    d.masks, d.boxes, d.count, d.row_offset = masks.data_ptr(), boxes.data_ptr(), count.data_ptr(), row_offset.data_ptr()
+    d.row_gt, d.live, d.targets = row_gt.data_ptr(), _req(live, torch.int32).data_ptr(), out.data_ptr()
+    d.B, d.max_gt, d.H, d.W, d.cap, d.rows, d.S = B, G, H, W, boxes.shape[1], rows, size
+    _lib.check(_lib.lib().a3d_mask_targets(C.byref(d), _stream()), "a3d_mask_targets")
+    return out
+
+
+def mask_loss_bytes(live_rows: int, P: int = 14, Cc: int = 256) -> int:
+    """Bytes a3d_mask_loss moves for `live_rows` rows: the activation read once, its gradient written once, the targets read."""
+    return live_rows * (2 * P * P * 4 * Cc * 4 + 4 * P * P) + _lib.lib().a3d_mask_loss_workspace_bytes() * 2
+
+
+def mask_loss(yu: torch.Tensor, targets: torch.Tensor, w: torch.Tensor, b: torch.Tensor, live: torch.Tensor, *,
+              dyu: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None):
+    """The fused predictor + BCE step of the mask head (a3d_mask_loss).  yu [rows, P, P, 4C] (the deconv's output after ReLU, unshuffled),
+    targets uint8 [rows, 2P, 2P], w [C], b [1], live: device int32.  -> (out [C + 2] = dw | db | loss, dyu like yu; rows past *live of
+    dyu / z are left as they are).  z: optional [rows, 2P, 2P] float32 to receive the logits."""
+    rows, P, P2, C4 = _req(yu).shape
+    Cc = C4 // 4
+    assert P == P2 and C4 == 4 * Cc and _req(w).numel() == Cc and _req(b).numel() == 1
+    assert tuple(_req(targets, torch.uint8).shape) == (rows, 2 * P, 2 * P)
+    if dyu is None:
+        dyu = torch.empty_like(yu)
+    if out is None:
+        out = torch.empty(Cc + 2, device=yu.device, dtype=torch.float32)
+    assert _req(dyu).shape == yu.shape and _req(out).numel() == Cc + 2
+    ws = torch.empty(_lib.lib().a3d_mask_loss_workspace_bytes() // 4, device=yu.device, dtype=torch.float32)
+    d = _lib.MaskLossDesc()
+    d.yu, d.targets, d.w, d.b, d.live = yu.data_ptr(), targets.data_ptr(), w.data_ptr(), b.data_ptr(), _req(live, torch.int32).data_ptr()
+    d.dyu, d.out, d.workspace = dyu.data_ptr(), out.data_ptr(), ws.data_ptr()
+    if z is not None:
+        assert tuple(_req(z).shape) == (rows, 2 * P, 2 * P)
+        d.z = z.data_ptr()
+    d.rows, d.P, d.C = rows, P, Cc
+    _lib.check(_lib.lib().a3d_mask_loss(C.byref(d), _stream()), "a3d_mask_loss")
+    return out, dyu
+
+
 def roi_align_fpn_backward(dfeats: Sequence[torch.Tensor], scales: Sequence[float], boxes: torch.Tensor, dout: torch.Tensor, *,
                            P: int, sampling_ratio: int, aligned: bool, count: Optional[torch.Tensor] = None,
                            row_offset: Optional[torch.Tensor] = None, scatter: bool = False) -> None:

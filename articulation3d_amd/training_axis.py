@@ -39,6 +39,32 @@ P14 = 14
 POOLED = 256 * P14 * P14  # 50176
 
 
+def foreground_rows(s: SolverCfg, cap: int, dev, aux, B: int) -> dict:
+    """select_foreground_proposals on the device (shared by the axis and the mask stage): per-image foreground counts of the sampled rows
+    (class < num_classes, sample order, at most `cap` per image), their prefix sum, the live total, and per compact row its proposal box,
+    image and matched ground truth."""
+    Rs = s.roi_batch_per_image
+    live_slot = torch.arange(Rs, device=dev)[None, :] < aux["roi_count"][:, None]
+    fg = live_slot & (aux["roi_cls"] < s.num_classes)
+    pos = torch.cumsum(fg.to(torch.int32), 1) - 1
+    keep = fg & (pos < cap)
+    count = keep.sum(1, dtype=torch.int32)
+    row_off = ops.count_offsets(count, cap)  # [B+1]: exclusive prefix sum, total last
+    img = torch.arange(B, device=dev, dtype=torch.int32)[:, None].expand(B, Rs)
+    trash = B * cap
+    slot = torch.where(keep, img * cap + pos, torch.full_like(pos, trash)).reshape(-1).long()  # per-image slot of the pooler's boxes
+    row = torch.where(keep, row_off[:-1, None] + pos, torch.full_like(pos, trash)).reshape(-1).long()  # compact row
+    boxes = torch.zeros(trash + 1, 4, device=dev)
+    boxes[slot] = aux["roi_boxes"].reshape(-1, 4)
+    gidx = torch.gather(aux["proposal_match"].long(), 1, aux["roi_index"].clamp(min=0).long()).to(torch.int32)
+    row_img = torch.zeros(trash + 1, device=dev, dtype=torch.int32)
+    row_gt = torch.zeros(trash + 1, device=dev, dtype=torch.int32)
+    row_img[row] = img.reshape(-1)
+    row_gt[row] = gidx.reshape(-1)
+    return dict(count=count, row_offset=row_off, live=row_off[B:].contiguous(), boxes=boxes[:trash].view(B, cap, 4),
+                row_img=row_img[:trash].contiguous(), row_gt=row_gt[:trash].contiguous())
+
+
 class AxisTrainer:
     """One training step of the step2_axis configuration: the frozen detector's forward pass, the axis head's forward and backward pass
     over the compacted foreground rows, the axis loss and the SGD update of roi_heads.axis_head.* -- all on the device.
@@ -156,31 +182,6 @@ class AxisTrainer:
     def autograd_anchor(self) -> torch.Tensor:
         return self.det.autograd_anchor()
 
-    # ------------------------------------------------------------------------------------------ foreground rows
-    def _foreground(self, aux, B):
-        """select_foreground_proposals on the device: per-image foreground counts of the sampled rows (class < num_classes, sample order),
-        their prefix sum, the live total, and per compact row its proposal box, image and matched ground truth."""
-        Rs, cap, dev = self.s.roi_batch_per_image, self.cap, self.dev
-        live_slot = torch.arange(Rs, device=dev)[None, :] < aux["roi_count"][:, None]
-        fg = live_slot & (aux["roi_cls"] < self.s.num_classes)
-        pos = torch.cumsum(fg.to(torch.int32), 1) - 1
-        keep = fg & (pos < cap)
-        count = keep.sum(1, dtype=torch.int32)
-        row_off = ops.count_offsets(count, cap)  # [B+1]: exclusive prefix sum, total last
-        img = torch.arange(B, device=dev, dtype=torch.int32)[:, None].expand(B, Rs)
-        trash = B * cap
-        slot = torch.where(keep, img * cap + pos, torch.full_like(pos, trash)).reshape(-1).long()  # per-image slot of the pooler's boxes
-        row = torch.where(keep, row_off[:-1, None] + pos, torch.full_like(pos, trash)).reshape(-1).long()  # compact row
-        boxes = torch.zeros(trash + 1, 4, device=dev)
-        boxes[slot] = aux["roi_boxes"].reshape(-1, 4)
-        gidx = torch.gather(aux["proposal_match"].long(), 1, aux["roi_index"].clamp(min=0).long()).to(torch.int32)
-        row_img = torch.zeros(trash + 1, device=dev, dtype=torch.int32)
-        row_gt = torch.zeros(trash + 1, device=dev, dtype=torch.int32)
-        row_img[row] = img.reshape(-1)
-        row_gt[row] = gidx.reshape(-1)
-        return dict(count=count, row_offset=row_off, live=row_off[B:].contiguous(), boxes=boxes[:trash].view(B, cap, 4),
-                    row_img=row_img[:trash].contiguous(), row_gt=row_gt[:trash].contiguous())
-
     # ------------------------------------------------------------------------------------------ the head
     def _conv(self, x, pk, m_dev, **kw):
         # precision 0: the fp32-input MFMA form, the one conv kernel form that honours a live row count (a3d_conv_desc.m_dev)
@@ -249,7 +250,7 @@ class AxisTrainer:
             gra[i, : len(r)] = r.detach().float().cpu()
             gta[i, : len(t)] = t.detach().float().cpu()
         gra, gta = gra.to(self.dev, non_blocking=True), gta.to(self.dev, non_blocking=True)
-        fgd = self._foreground(aux, B)
+        fgd = foreground_rows(s, self.cap, self.dev, aux, B)
         if samples is not None:  # (given index sets: host control flow is allowed here; the cap must hold)
             assert int((aux["roi_cls"][:, :] < s.num_classes).logical_and(
                 torch.arange(s.roi_batch_per_image, device=self.dev)[None] < aux["roi_count"][:, None]).sum(1).max()) <= self.cap, \

@@ -35,7 +35,7 @@ int a3d_version(void);
 /* sizeof() of a descriptor struct, for bindings to verify their mirror of the layout.  id: 0 a3d_conv_desc, 1 a3d_rpn_desc,
  * 2 a3d_boxdet_desc, 3 a3d_roialign_desc, 4 a3d_paste_desc, 5 a3d_pack_desc, 6 a3d_wgrad_desc, 7 a3d_roialign_bwd_desc,
  * 8 a3d_match_desc, 9 a3d_rpn_loss_desc, 10 a3d_box_loss_desc, 11 a3d_roi_sample_desc, 12 a3d_sweep_desc, 13 a3d_transpose_item,
- * 14 a3d_axis_loss_desc; 0 for an unknown id. */
+ * 14 a3d_axis_loss_desc, 15 a3d_mask_targets_desc, 16 a3d_mask_loss_desc; 0 for an unknown id. */
 size_t a3d_struct_size(int id);
 
 /* ------------------------------------------------------------------------------------------------
@@ -550,6 +550,52 @@ typedef struct a3d_axis_loss_desc {
     float beta, loss_weight;
 } a3d_axis_loss_desc;
 int a3d_axis_loss(const a3d_axis_loss_desc *d, void *stream);
+
+/* Mask head's training step (the mask share of config/step3_plane.yaml; detectron2 mask_rcnn_loss with bitmask ground truth), csrc/mask_train.hip.
+ *
+ * a3d_mask_targets: BitMasks.crop_and_resize(proposal_boxes, S) of the matched ground-truth mask per compact foreground row:
+ *   targets[r] = ROIAlign((S, S), 1.0, sampling_ratio 0, aligned)(mask[b][row_gt[r]], box of row r) >= 0.5, uint8 0 / 1, fp32 arithmetic.
+ * Half-pixel offset, no clamp of the box size, grid ceil(roi_h / S) x ceil(roi_w / S) per bin, divisor max(grid, 1), samples outside
+ * [-1, H] x [-1, W] count as 0, the border rule of the pooler.  Row r belongs to image b with row_offset[b] <= r < row_offset[b + 1]; its box
+ * is boxes[b][r - row_offset[b]].  A box without area (or not finite, or more than 32768 samples per bin on a side -- not a proposal of
+ * any image) and a row whose slot / ground-truth index is out of range give an all-zero target.  Rows past *live are neither read nor
+ * written.  No atomics, a fixed summation order: bit-reproducible. */
+typedef struct a3d_mask_targets_desc {
+    const uint8_t *masks;   /* [B, max_gt, H, W] 0 / non-zero */
+    const float *boxes;     /* [B, cap, 4] */
+    const int *count;       /* [B] live slots per image */
+    const int *row_offset;  /* [B+1] exclusive prefix sum of count */
+    const int *row_gt;      /* [rows] */
+    const int *live;        /* DEVICE int: live rows (<= rows) */
+    uint8_t *targets;       /* [rows, S, S] */
+    int B, max_gt, H, W, cap, rows, S;
+    int pad_;
+} a3d_mask_targets_desc;
+int a3d_mask_targets(const a3d_mask_targets_desc *d, void *stream);
+
+/* a3d_mask_loss: the class-agnostic 256 -> 1 predictor, the mean BCE-with-logits and their backward pass in ONE pass over the deconv's
+ * activation.  yu [rows, P, P, 4 * C]: the 2x2-stride-2 deconv's output after ReLU in UNSHUFFLED layout, channel (dy, dx, co) of input
+ * pixel (iy, ix) = output pixel (2 iy + dy, 2 ix + dx), channel co.  Per live output pixel
+ *   z = w . yu[pixel] + b,  t = targets[r][2 iy + dy][2 ix + dx],  loss += max(z, 0) - z t + log1p(exp(-|z|)),
+ *   dz = (sigmoid(z) - t) / (*live * 4 P P),  dyu = dz * w * (yu > 0),  dw += dz * yu,  db += dz.
+ * yu is read once and dyu written once; dw [C], db and the loss leave through per-workgroup partials (workspace) and a second launch
+ * that sums them in a fixed order -- no atomics, the same bits on every run.  out = [dw (C) | db | loss].  *live == 0: loss 0 and every
+ * gradient exactly 0.  Rows past *live are neither read nor written (dyu, z).  C == 256 (one wave, four channels per lane). */
+typedef struct a3d_mask_loss_desc {
+    const float *yu;         /* [rows, P, P, 4C] */
+    const uint8_t *targets;  /* [rows, 2P, 2P] */
+    const float *w;          /* [C] */
+    const float *b;          /* [1] */
+    const int *live;         /* DEVICE int */
+    float *dyu;              /* [rows, P, P, 4C] */
+    float *z;                /* [rows, 2P, 2P] logits, or NULL */
+    float *out;              /* [C + 2]: dw | db | loss */
+    float *workspace;        /* a3d_mask_loss_workspace_bytes() */
+    int rows, P, C;
+    int pad_;
+} a3d_mask_loss_desc;
+size_t a3d_mask_loss_workspace_bytes(void);
+int a3d_mask_loss(const a3d_mask_loss_desc *d, void *stream);
 
 /* Gradient of a3d_roi_align_fpn with respect to the pyramid: dfeat[level] += scatter(dout).  dfeat must hold the
  * gradient accumulated so far (or zeros).  Adaptive sampling (sampling_ratio 0) only: the box pooler. */
