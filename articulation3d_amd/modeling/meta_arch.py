@@ -13,6 +13,7 @@ Two entry points share the same kernels:
 """
 from __future__ import annotations
 
+import importlib
 import os
 from dataclasses import dataclass
 from typing import List, Optional
@@ -23,7 +24,7 @@ from torch import nn
 from .. import ops
 from ..registry import META_ARCH_REGISTRY
 from ..streams import SMALL_BATCH
-from ..structures import Boxes, ImageList, Instances, gt_bitmasks
+from ..structures import Boxes, ImageList, Instances
 from .backbone import build_backbone
 from .depth_head import build_depth_head
 from .layers import to_nchw_view
@@ -37,6 +38,9 @@ POST_SCORE_THRESH = 0.1  # planercnn.py:217
 # training stage 3 (the mask share of config/step3_plane.yaml): the head that trains, and the heads that must be off or in MODEL.FREEZE
 STAGE3_TRAINABLE = "roi_heads.mask_head"
 STAGE3_FROZEN_HEADS = ("roi_heads.plane_head", "roi_heads.axis_head", "depth_head")
+# training stage -> (module, class) of its trainer, imported on first use.  Each class's static `batch_extras(batched_inputs)` gives the
+# ground truth its forward_backward takes after gt_classes: none, (gt_rot_axis, gt_tran_axis), (gt_masks,)
+STAGE_TRAINER = {1: ("..training", "DetectorTrainer"), 2: ("..training_axis", "AxisTrainer"), 3: ("..training_mask", "MaskTrainer")}
 
 
 @dataclass
@@ -295,22 +299,16 @@ class PlaneRCNN(nn.Module):
     def trainer(self, solver=None, precision: str = "bf16x3"):
         """The hand-written training step behind the reference's training-mode call: created on first use (it copies every
         trainable parameter into its flat buffer).  `articulation3d_amd.engine.build_optimizer` returns the optimiser bound to it.
-        Stage 1: DetectorTrainer; stage 2: training_axis.AxisTrainer; stage 3: training_mask.MaskTrainer (see training_stage)."""
+        The class comes from STAGE_TRAINER (see training_stage)."""
         if getattr(self, "_trainer", None) is None:
-            stage = self.training_stage()
-            if stage == 3:
-                from ..training_mask import MaskTrainer
-
-                self._trainer = MaskTrainer(self, solver, precision=precision)
-            elif stage == 2:
-                from ..training_axis import AxisTrainer
-
-                self._trainer = AxisTrainer(self, solver, precision=precision)
-            else:
-                from ..training import DetectorTrainer
-
-                self._trainer = DetectorTrainer(self, solver, precision=precision)
+            self._trainer = self._trainer_class()(self, solver, precision=precision)
         return self._trainer
+
+    def _trainer_class(self):
+        if getattr(self, "_trainer", None) is not None:
+            return type(self._trainer)
+        module, name = STAGE_TRAINER[self.training_stage()]
+        return getattr(importlib.import_module(module, __package__), name)
 
     def training_forward(self, batched_inputs):
         """`model(batched_inputs)` in training mode, as detectron2's SimpleTrainer.run_step calls it (tools/train_net.py:84-104 ->
@@ -321,7 +319,7 @@ class PlaneRCNN(nn.Module):
         scalars accept `.backward()` so the reference's loop body stays as it is, and `engine.build_optimizer(cfg, model).step()`
         applies the fused all-reduce + SGD launch.  Only the step1_bbox configuration (BASELINE configs[4]: box branch; mask /
         plane / axis / depth heads off) has a training path."""
-        stage = self.training_stage()
+        cls = self._trainer_class()
         assert "instances" in batched_inputs[0], "training needs ground-truth instances (planercnn.py:84-85)"
         imgs = [x["image"] for x in batched_inputs]
         assert all(tuple(t.shape) == tuple(imgs[0].shape) for t in imgs), "one image size per batch (the reference trains on 480x640 frames)"
@@ -330,17 +328,9 @@ class PlaneRCNN(nn.Module):
             frames = frames.round().clamp(0, 255).to(torch.uint8)  # (detectron2's mapper hands over uint8; tolerate float 0-255)
         gt_boxes = [x["instances"].gt_boxes.tensor.float() for x in batched_inputs]
         gt_classes = [x["instances"].gt_classes.long() for x in batched_inputs]
-        if stage == 3:  # (polygon ground truth is refused before anything is built or run: NotImplementedError)
-            masks = [gt_bitmasks(x["instances"].gt_masks) for x in batched_inputs]
+        extra = cls.batch_extras(batched_inputs)  # (stage 3: polygon ground truth is refused before anything is built or run)
         tr = self.trainer()
-        if stage == 3:  # configs/step3_mask.yaml: {loss_cls, loss_box_reg} of the frozen detector + loss_mask
-            losses, _aux = tr.forward_backward(frames, gt_boxes, gt_classes, masks, exchange=True)
-        elif stage == 2:  # step2_axis.yaml: {loss_cls, loss_box_reg} of the frozen detector + {loss_rot_axis, loss_tran_axis}
-            rot = [x["instances"].gt_rot_axis.float() for x in batched_inputs]
-            tran = [x["instances"].gt_tran_axis.float() for x in batched_inputs]
-            losses, _aux = tr.forward_backward(frames, gt_boxes, gt_classes, rot, tran, exchange=True)
-        else:
-            losses, _aux = tr.forward_backward(frames, gt_boxes, gt_classes, exchange=True)  # (optimizer.step() finishes the exchange)
+        losses, _aux = tr.forward_backward(frames, gt_boxes, gt_classes, *extra, exchange=True)  # (optimizer.step() finishes the exchange)
         names = list(losses)
         outs = _StepLosses.apply(tr.autograd_anchor(), *[losses[k] for k in names])
         return dict(zip(names, outs))

@@ -816,6 +816,11 @@ class DetectorTrainer:
                    proposals=(pb, pcount), heads=heads, feats=feats, pred=pred.view(M, 32), roi_boxes=roi_boxes, anchor_match=(midx, lab))
         return losses, aux
 
+    @staticmethod
+    def batch_extras(batched_inputs) -> tuple:
+        """The ground truth beyond boxes and classes that `forward_backward` takes from a batch of the reference's training-mode call."""
+        return ()
+
     def autograd_anchor(self) -> torch.Tensor:
         """A leaf that requires grad, so that the loss scalars handed out by PlaneRCNN.training_forward can be `.backward()`-ed."""
         if getattr(self, "_anchor", None) is None:

@@ -16,7 +16,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import torch
 
@@ -47,35 +46,17 @@ def cap_targets(model, dev, n, g=64):
 
 def leg(model, dev, precision, batch, steps, warmup, targets, max_gt=16):
     from train_axis_exchange_check import axis_targets
+    from train_head_bench import head_leg
     from articulation3d_amd.training import SolverCfg
     from articulation3d_amd.training_axis import AxisTrainer
     from articulation3d_amd.utils.synthetic import synthetic_frames
 
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats(dev)
-    tr = AxisTrainer(model, SolverCfg(max_gt=max_gt), seed=2020, precision=precision)
     frames = torch.from_numpy(synthetic_frames(batch, seed=2020)).to(dev)
-    gtb, gtc = [t[0] for t in targets], [t[1] for t in targets]
-    rot, tran = axis_targets(targets, 7)
-    for _ in range(warmup):
-        tr.step(frames, gtb, gtc, rot, tran)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        losses, aux = tr.step(frames, gtb, gtc, rot, tran)
-    torch.cuda.synchronize()
-    el = time.perf_counter() - t0
-    tr.phase_events = []  # one instrumented step
-    losses, aux = tr.step(frames, gtb, gtc, rot, tran)
-    torch.cuda.synchronize()
-    ev = tr.phase_events
-    split = {ev[i][0]: round(ev[i - 1][1].elapsed_time(ev[i][1]), 3) for i in range(1, len(ev))}
-    fg = aux["fg"]["count"].float().cpu()
-    out = {"precision": precision, "images_per_gpu": batch, "images_per_s": round(batch * steps / el, 2), "ms_per_step": round(1e3 * el / steps, 3),
-           "fg_rows_per_image": round(float(fg.mean()), 2), "fg_rows_min": int(fg.min()), "fg_rows_max": int(fg.max()), "ms_split": split,
-           "peak_mem_gib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2),
-           "losses": {k: round(float(v), 5) for k, v in losses.items()}}
-    del tr
+    args = (frames, [t[0] for t in targets], [t[1] for t in targets], *axis_targets(targets, 7))
+    out, _tr, aux = head_leg(lambda: AxisTrainer(model, SolverCfg(max_gt=max_gt), seed=2020, precision=precision), args, dev, precision,
+                             batch, steps, warmup)
+    fg = aux["fg"]["count"]
+    out.update(fg_rows_min=int(fg.min()), fg_rows_max=int(fg.max()))
     return out
 
 

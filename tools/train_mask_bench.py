@@ -17,7 +17,6 @@ import json
 import os
 import statistics
 import sys
-import time
 
 import torch
 
@@ -35,43 +34,29 @@ def ellipse_masks(boxes, H=480, W=640):
 
 
 def leg(model, dev, precision, batch, steps, warmup, targets):
+    from train_head_bench import head_leg
     from articulation3d_amd import train_ops as T
     from articulation3d_amd.training import SolverCfg
     from articulation3d_amd.training_mask import MaskTrainer
     from articulation3d_amd.utils.synthetic import synthetic_frames
 
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats(dev)
-    tr = MaskTrainer(model, SolverCfg(), seed=2020, precision=precision)
     frames = torch.from_numpy(synthetic_frames(batch, seed=2020)).to(dev)
-    gtb, gtc = [t[0] for t in targets], [t[1] for t in targets]
-    gtm = [ellipse_masks(t[0]).to(dev) for t in targets]
-    for _ in range(warmup):
-        tr.step(frames, gtb, gtc, gtm)
-    torch.cuda.synchronize()
-    tr.kernel_events = []
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        losses, aux = tr.step(frames, gtb, gtc, gtm)
-    torch.cuda.synchronize()
-    el = time.perf_counter() - t0
-    kernel_ms = statistics.median(a.elapsed_time(b) for a, b in tr.kernel_events)
-    tr.kernel_events = None
-    tr.phase_events = []  # one instrumented step
-    losses, aux = tr.step(frames, gtb, gtc, gtm)
-    torch.cuda.synchronize()
-    ev = tr.phase_events
-    split = {ev[i][0]: round(ev[i - 1][1].elapsed_time(ev[i][1]), 3) for i in range(1, len(ev))}
-    fg = aux["fg"]["count"].float().cpu()
-    live = int(aux["fg"]["live"])
+    args = (frames, [t[0] for t in targets], [t[1] for t in targets], [ellipse_masks(t[0]).to(dev) for t in targets])
+    kernel_ms = []
+
+    def start_kernel_events(tr):
+        tr.kernel_events = []
+
+    def read_kernel_events(tr):  # a3d_mask_loss over the timed steps only: the instrumented step runs without these events
+        kernel_ms.append(statistics.median(a.elapsed_time(b) for a, b in tr.kernel_events))
+        tr.kernel_events = None
+
+    out, tr, aux = head_leg(lambda: MaskTrainer(model, SolverCfg(), seed=2020, precision=precision), args, dev, precision, batch, steps,
+                            warmup, start_kernel_events, read_kernel_events)
+    live, ms = int(aux["fg"]["live"]), kernel_ms[0]
     nbytes = T.mask_loss_bytes(live, tr.pool_size, tr.dim)
-    out = {"precision": precision, "images_per_gpu": batch, "images_per_s": round(batch * steps / el, 2), "ms_per_step": round(1e3 * el / steps, 3),
-           "fg_rows": live, "fg_rows_per_image": round(float(fg.mean()), 2), "ms_split": split,
-           "mask_loss": {"ms": round(kernel_ms, 4), "bytes": nbytes, "tb_per_s": round(nbytes / (kernel_ms * 1e-3) / 1e12, 3),
-                         "share_of_hbm_rate": round(nbytes / (kernel_ms * 1e-3) / HBM_BYTES_PER_S, 3)},
-           "peak_mem_gib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2),
-           "losses": {k: round(float(v), 5) for k, v in losses.items()}}
-    del tr
+    out.update(fg_rows=live, mask_loss={"ms": round(ms, 4), "bytes": nbytes, "tb_per_s": round(nbytes / (ms * 1e-3) / 1e12, 3),
+                                        "share_of_hbm_rate": round(nbytes / (ms * 1e-3) / HBM_BYTES_PER_S, 3)})
     return out
 
 
