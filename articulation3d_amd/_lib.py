@@ -151,6 +151,15 @@ class MaskLossDesc(C.Structure):
     ]
 
 
+class PlaneLossDesc(C.Structure):
+    _fields_ = [
+        ("h", fptr), ("w", fptr), ("b", fptr), ("live", fptr), ("row_img", fptr), ("row_gt", fptr), ("gt_planes", fptr),
+        ("workspace", fptr), ("out", fptr), ("dh", fptr), ("raw", fptr),
+        ("rows", C.c_int), ("K", C.c_int), ("B", C.c_int), ("max_gt", C.c_int),
+        ("loss_weight", C.c_float), ("normal_only", C.c_int),
+    ]
+
+
 class TransposeItem(C.Structure):
     _fields_ = [("w", fptr), ("scale", fptr), ("wt", fptr), ("Cout", C.c_int), ("KH", C.c_int), ("KW", C.c_int), ("Cin", C.c_int),
                 ("block0", C.c_int), ("pad_", C.c_int)]
@@ -280,6 +289,8 @@ SIGNATURES = {
     "a3d_mask_targets": (C.c_int, [C.POINTER(MaskTargetsDesc), fptr]),
     "a3d_mask_loss_workspace_bytes": (C.c_size_t, []),
     "a3d_mask_loss": (C.c_int, [C.POINTER(MaskLossDesc), fptr]),
+    "a3d_plane_loss_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "a3d_plane_loss": (C.c_int, [C.POINTER(PlaneLossDesc), fptr]),
     "a3d_roi_align_fpn_backward": (C.c_int, [C.POINTER(RoiAlignBwdDesc), fptr]),
     "a3d_roi_align_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(RoiAlignBwdDesc)]),
     "a3d_roi_align_fpn_backward_gather": (C.c_int, [C.POINTER(RoiAlignBwdDesc), fptr, fptr]),
@@ -302,7 +313,7 @@ SIGNATURES = {
 
 STRUCT_IDS = {0: ConvDesc, 1: RpnDesc, 2: BoxDetDesc, 3: RoiAlignDesc, 4: PasteDesc, 5: PackDesc, 6: WgradDesc,
               7: RoiAlignBwdDesc, 8: MatchDesc, 9: RpnLossDesc, 10: BoxLossDesc, 11: RoiSampleDesc, 12: SweepDesc, 13: TransposeItem,
-              14: AxisLossDesc, 15: MaskTargetsDesc, 16: MaskLossDesc}
+              14: AxisLossDesc, 15: MaskTargetsDesc, 16: MaskLossDesc, 17: PlaneLossDesc}
 
 _lib = None
 

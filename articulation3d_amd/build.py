@@ -47,6 +47,7 @@ SOURCES = {
     "train_ops.hip": ["-ffp-contract=off"],  # matcher IoU / box deltas round like the reference's separate mul, add, div
     "axis_train.hip": ["-ffp-contract=off"],  # normalise / double angle / smooth L1 round like the reference's separate operators
     "mask_train.hip": ["-ffp-contract=off"],  # mask-target sample coordinates round like the pooler's (the dot product asks for its FMAs)
+    "plane_train.hip": ["-ffp-contract=off"],  # normalise / L1 round like the reference's separate operators (the dot products ask for their FMAs)
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 COMMON += os.environ.get("A3D_HIPCC_FLAGS", "").split()  # developer builds only (e.g. -DA3D_ABLATIONS: timing-only kernel variants)

@@ -190,6 +190,7 @@ extern "C" size_t a3d_struct_size(int id) {
         case 14: return sizeof(a3d_axis_loss_desc);
         case 15: return sizeof(a3d_mask_targets_desc);
         case 16: return sizeof(a3d_mask_loss_desc);
+        case 17: return sizeof(a3d_plane_loss_desc);
         default: return 0;
     }
 }

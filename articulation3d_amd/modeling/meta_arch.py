@@ -38,9 +38,13 @@ POST_SCORE_THRESH = 0.1  # planercnn.py:217
 # training stage 3 (the mask share of config/step3_plane.yaml): the head that trains, and the heads that must be off or in MODEL.FREEZE
 STAGE3_TRAINABLE = "roi_heads.mask_head"
 STAGE3_FROZEN_HEADS = ("roi_heads.plane_head", "roi_heads.axis_head", "depth_head")
+# training stage 4 (the plane share of config/step3_plane.yaml): the same rule with the plane head trainable and the mask head off or frozen
+STAGE4_TRAINABLE = "roi_heads.plane_head"
+STAGE4_FROZEN_HEADS = ("roi_heads.mask_head", "roi_heads.axis_head", "depth_head")
 # training stage -> (module, class) of its trainer, imported on first use.  Each class's static `batch_extras(batched_inputs)` gives the
-# ground truth its forward_backward takes after gt_classes: none, (gt_rot_axis, gt_tran_axis), (gt_masks,)
-STAGE_TRAINER = {1: ("..training", "DetectorTrainer"), 2: ("..training_axis", "AxisTrainer"), 3: ("..training_mask", "MaskTrainer")}
+# ground truth its forward_backward takes after gt_classes: none, (gt_rot_axis, gt_tran_axis), (gt_masks,), (gt_planes,)
+STAGE_TRAINER = {1: ("..training", "DetectorTrainer"), 2: ("..training_axis", "AxisTrainer"), 3: ("..training_mask", "MaskTrainer"),
+                 4: ("..training_plane", "PlaneTrainer")}
 
 
 @dataclass
@@ -276,8 +280,10 @@ class PlaneRCNN(nn.Module):
         """Which training stage this model's configuration is: 1 (config/step1_bbox.yaml: box branch only), 2 (config/step2_axis.yaml:
         AXIS_ON, MASK / PLANE / DEPTH off, FREEZE covering the four detector modules) or 3, the MASK SHARE of config/step3_plane.yaml
         (configs/step3_mask.yaml: MASK_ON with roi_heads.mask_head trainable, FREEZE covering the four detector modules, and each of the
-        plane, axis and depth heads either off or frozen -- the reference skips a frozen head in training the same way).  Anything else
-        (step3_plane.yaml's own flags, whose plane and depth losses have no training path, among it) raises NotImplementedError."""
+        plane, axis and depth heads either off or frozen -- the reference skips a frozen head in training the same way) or 4, its PLANE
+        SHARE (configs/step3_planehead.yaml: PLANE_ON with roi_heads.plane_head trainable, the same FREEZE rule with the mask head in the
+        plane head's place).  Anything else (step3_plane.yaml's own flags, which train the mask, plane and depth losses in one joint
+        step, among it) raises NotImplementedError."""
         rh = self.roi_heads
         mask, plane, axis = (bool(getattr(rh, n, False)) for n in ("mask_on", "plane_on", "axis_on"))
         others = self.depth_head_on or mask or plane
@@ -286,15 +292,18 @@ class PlaneRCNN(nn.Module):
             return 1
         if not others and axis and set(self.STAGE2_FREEZE) <= frozen:
             return 2
-        on = {"roi_heads.plane_head": plane, "roi_heads.axis_head": axis, "depth_head": bool(self.depth_head_on)}
-        if (mask and STAGE3_TRAINABLE not in frozen and set(self.STAGE2_FREEZE) <= frozen
-                and all(not on[h] or h in frozen for h in STAGE3_FROZEN_HEADS)):
-            return 3
+        on = {"roi_heads.mask_head": mask, "roi_heads.plane_head": plane, "roi_heads.axis_head": axis, "depth_head": bool(self.depth_head_on)}
+        for stage, head, rest in ((3, STAGE3_TRAINABLE, STAGE3_FROZEN_HEADS), (4, STAGE4_TRAINABLE, STAGE4_FROZEN_HEADS)):
+            if on[head] and head not in frozen and set(self.STAGE2_FREEZE) <= frozen and all(not on[h] or h in frozen for h in rest):
+                return stage
         raise NotImplementedError("training is implemented for config/step1_bbox.yaml (MASK_ON / PLANE_ON / AXIS_ON / DEPTH_ON false), "
                                   "config/step2_axis.yaml (AXIS_ON true, MASK_ON / PLANE_ON / DEPTH_ON false, FREEZE: " + str(list(self.STAGE2_FREEZE)) +
-                                  ") and the mask share of step3_plane.yaml (configs/step3_mask.yaml: MASK_ON true, " + STAGE3_TRAINABLE +
+                                  "), the mask share of step3_plane.yaml (configs/step3_mask.yaml: MASK_ON true, " + STAGE3_TRAINABLE +
                                   " trainable, FREEZE covering the detector and every other head that is on: " + str(list(STAGE3_FROZEN_HEADS)) +
-                                  "); the plane and depth losses of step3_plane.yaml are out of scope")
+                                  ") and its plane share (configs/step3_planehead.yaml: PLANE_ON true, " + STAGE4_TRAINABLE +
+                                  " trainable, FREEZE covering the detector and " + str(list(STAGE4_FROZEN_HEADS)) +
+                                  "); step3_plane.yaml's own flags, which train the mask, plane and depth losses in one joint step, and the "
+                                  "depth loss are out of scope")
 
     def trainer(self, solver=None, precision: str = "bf16x3"):
         """The hand-written training step behind the reference's training-mode call: created on first use (it copies every
@@ -314,7 +323,8 @@ class PlaneRCNN(nn.Module):
         """`model(batched_inputs)` in training mode, as detectron2's SimpleTrainer.run_step calls it (tools/train_net.py:84-104 ->
         planercnn.py:83-123): list of {"image": CHW uint8 BGR, "instances": Instances(gt_boxes, gt_classes)} -> the loss dict
         {loss_cls, loss_box_reg, loss_rpn_cls, loss_rpn_loc} (stage 2: + the axis losses; stage 3: Instances carry gt_masks, a
-        structures.BitMasks or a [G,H,W] tensor, and the dict is {loss_cls, loss_box_reg, loss_mask}).  There is no autograd graph: the call runs forward AND backward
+        structures.BitMasks or a [G,H,W] tensor, and the dict is {loss_cls, loss_box_reg, loss_mask}; stage 4: Instances carry gt_planes [G,3]
+        and the dict is {loss_cls, loss_box_reg, loss_plane}).  There is no autograd graph: the call runs forward AND backward
         (DetectorTrainer.forward_backward) and leaves the gradients of the summed loss in the trainer's flat buffer; the returned
         scalars accept `.backward()` so the reference's loop body stays as it is, and `engine.build_optimizer(cfg, model).step()`
         applies the fused all-reduce + SGD launch.  Only the step1_bbox configuration (BASELINE configs[4]: box branch; mask /
@@ -328,7 +338,7 @@ class PlaneRCNN(nn.Module):
             frames = frames.round().clamp(0, 255).to(torch.uint8)  # (detectron2's mapper hands over uint8; tolerate float 0-255)
         gt_boxes = [x["instances"].gt_boxes.tensor.float() for x in batched_inputs]
         gt_classes = [x["instances"].gt_classes.long() for x in batched_inputs]
-        extra = cls.batch_extras(batched_inputs)  # (stage 3: polygon ground truth is refused before anything is built or run)
+        extra = cls.batch_extras(batched_inputs)  # (stage 3: polygon ground truth, stage 4: malformed gt_planes -- refused before anything is built or run)
         tr = self.trainer()
         losses, _aux = tr.forward_backward(frames, gt_boxes, gt_classes, *extra, exchange=True)  # (optimizer.step() finishes the exchange)
         names = list(losses)
@@ -338,7 +348,7 @@ class PlaneRCNN(nn.Module):
     def train(self, mode: bool = True):
         """Leaving training mode writes the trainer's parameters back into the modules (inference packs its weights from them)."""
         if not mode and getattr(self, "_trainer", None) is not None and self.training:
-            self.load_state_dict(self._trainer.export_state_dict(), strict=False)  # (stage 2 / 3: the axis / mask head's entries only)
+            self.load_state_dict(self._trainer.export_state_dict(), strict=False)  # (stage 2 / 3 / 4: the axis / mask / plane head's entries only)
         return super().train(mode)
 
     # batches up to this size run the depth decoder on a second HIP stream beside the ROI branch (0 disables: every kernel then runs alone)

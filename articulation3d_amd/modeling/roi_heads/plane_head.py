@@ -71,7 +71,8 @@ class PlaneRCNNConvFCHead(nn.Module):
     def forward(self, x, instances):
         """Reference signature (plane_head.py:71-89): x = pooled NCHW features; mutates and returns instances."""
         if self.training:
-            raise NotImplementedError("plane loss (training) is outside the inference hot path (SURVEY.md 8f-1)")
+            raise NotImplementedError("the module-level call has no autograd path: the plane head trains through training_plane.PlaneTrainer "
+                                      "(configs/step3_planehead.yaml; PlaneRCNN.trainer())")
         planes = self.forward_rows(to_nhwc(x)) if x.shape[0] else x.new_zeros((0, self.param_pred.out_features))
         plane_rcnn_inference(planes, instances)
         return instances

@@ -287,6 +287,41 @@ def mask_loss(yu: torch.Tensor, targets: torch.Tensor, w: torch.Tensor, b: torch
     return out, dyu
 
 
+_PLANE_WS: dict = {}  # (device, K) -> the per-wave partials of a3d_plane_loss (launches of one device's stream follow one another)
+
+
+def plane_loss(h: torch.Tensor, w: torch.Tensor, b: torch.Tensor, live: torch.Tensor, row_img: torch.Tensor, row_gt: torch.Tensor,
+               gt_planes: torch.Tensor, *, loss_weight: float = 1.0, normal_only: bool = True, out: Optional[torch.Tensor] = None,
+               dh: Optional[torch.Tensor] = None, raw: Optional[torch.Tensor] = None):
+    """The fused predictor + normalise + L1 step of the plane head (a3d_plane_loss).  h [rows, K] (the FC's output after ReLU), w [3, K],
+    b [3], live: device int32, row_img / row_gt [rows] int32, gt_planes [B, max_gt, 3].  -> (out [3K + 4] = dw | db | loss, dh like h;
+    rows past *live of dh / raw are left as they are).  raw: optional [rows, 3] float32 to receive the predictor's output before
+    F.normalize."""
+    rows, K = _req(h).shape
+    B, G = _req(gt_planes).shape[:2]
+    assert _req(w).numel() == 3 * K and _req(b).numel() == 3 and gt_planes.dim() == 3 and gt_planes.shape[2] == 3
+    assert _req(row_img, torch.int32).numel() >= rows and _req(row_gt, torch.int32).numel() >= rows
+    if dh is None:
+        dh = torch.empty_like(h)
+    if out is None:
+        out = torch.empty(3 * K + 4, device=h.device, dtype=torch.float32)
+    assert _req(dh).shape == h.shape and _req(out).numel() == 3 * K + 4
+    ws = _PLANE_WS.get((h.device, K))
+    if ws is None:
+        ws = _PLANE_WS[(h.device, K)] = torch.empty(max(4, _lib.lib().a3d_plane_loss_workspace_bytes(K) // 4), device=h.device, dtype=torch.float32)
+    d = _lib.PlaneLossDesc()
+    d.h, d.w, d.b, d.live = h.data_ptr(), w.data_ptr(), b.data_ptr(), _req(live, torch.int32).data_ptr()
+    d.row_img, d.row_gt, d.gt_planes = row_img.data_ptr(), row_gt.data_ptr(), gt_planes.data_ptr()
+    d.workspace, d.out, d.dh = ws.data_ptr(), out.data_ptr(), dh.data_ptr()
+    if raw is not None:
+        assert tuple(_req(raw).shape) == (rows, 3)
+        d.raw = raw.data_ptr()
+    d.rows, d.K, d.B, d.max_gt = rows, K, B, G
+    d.loss_weight, d.normal_only = float(loss_weight), int(bool(normal_only))
+    _lib.check(_lib.lib().a3d_plane_loss(C.byref(d), _stream()), "a3d_plane_loss")
+    return out, dh
+
+
 def roi_align_fpn_backward(dfeats: Sequence[torch.Tensor], scales: Sequence[float], boxes: torch.Tensor, dout: torch.Tensor, *,
                            P: int, sampling_ratio: int, aligned: bool, count: Optional[torch.Tensor] = None,
                            row_offset: Optional[torch.Tensor] = None, scatter: bool = False) -> None:

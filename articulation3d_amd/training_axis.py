@@ -32,7 +32,7 @@ import torch
 from . import ops, train_ops as T
 from .ops import ACT_NONE, ACT_RELU
 from .training import SolverCfg, _Layer
-from .training_head import HeadTrainer
+from .training_head import HeadTrainer, fc_columns_to_chw, fc_columns_to_hwc
 
 AXIS_TOWER_STREAM = os.environ.get("A3D_TRAIN_AXIS_STREAM", "1") != "0"  # the T tower on a second stream beside R (same bits)
 AH = "roi_heads.axis_head."
@@ -85,7 +85,7 @@ class AxisTrainer(HeadTrainer):
         if ly.sources:
             return [kv for prefix, r0, nr in ly.sources for kv in ((prefix + ".weight", w[r0:r0 + nr]), (prefix + ".bias", b[r0:r0 + nr]))]
         # the FC: columns stored in the HWC order of the NHWC activations, the reference's are CHW
-        return [(ly.name + ".weight", w.view(ly.rows, P14, P14, 256).permute(0, 3, 1, 2).reshape(ly.rows, -1)), (ly.name + ".bias", b)]
+        return [(ly.name + ".weight", fc_columns_to_chw(w, 256, P14)), (ly.name + ".bias", b)]
 
     def _load_odd(self, ly: _Layer, sd):
         if ly.sources:
@@ -95,8 +95,7 @@ class AxisTrainer(HeadTrainer):
                 ly.w[r0:r0 + nr] = sd[prefix + ".weight"].reshape(nr, -1).to(self.dev)
                 ly.b[r0:r0 + nr] = sd[prefix + ".bias"].to(self.dev)
         else:
-            w = sd[ly.name + ".weight"].to(self.dev).float().view(ly.rows, 256, P14, P14).permute(0, 2, 3, 1)
-            ly.w.copy_(w.reshape(ly.rows, -1))
+            ly.w.copy_(fc_columns_to_hwc(sd[ly.name + ".weight"].to(self.dev).float(), 256, P14))
             ly.b.copy_(sd[ly.name + ".bias"].to(self.dev))
 
     # ------------------------------------------------------------------------------------------ the head

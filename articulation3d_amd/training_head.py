@@ -1,4 +1,5 @@
-"""The scaffold every head trainer over the frozen detector shares (training_axis.AxisTrainer, training_mask.MaskTrainer).
+"""The scaffold every head trainer over the frozen detector shares (training_axis.AxisTrainer, training_mask.MaskTrainer,
+training_plane.PlaneTrainer).
 
 `HeadTrainer` owns, once:
   * the frozen detector (a `DetectorTrainer` driven through `frozen_forward`: stage 1's launches, precision, storage and ROI sampling seed)
@@ -50,6 +51,17 @@ def flat_layout(layers: Sequence[_Layer], bias_rows: Optional[Dict[str, int]] = 
         off += n
     ends.append((off + 3) // 4 * 4)
     return FlatLayout(out, tails, ends[-1], list(zip(ends[:-1], ends[1:])))
+
+
+def fc_columns_to_hwc(w: torch.Tensor, channels: int, size: int) -> torch.Tensor:
+    """A flattening FC's weight (or its gradient) [rows, channels * size * size] with the reference's CHW column order -> the HWC order of
+    the NHWC activations, what the inference `Linear(chw=...)` does."""
+    return w.reshape(w.shape[0], channels, size, size).permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+
+
+def fc_columns_to_chw(w: torch.Tensor, channels: int, size: int) -> torch.Tensor:
+    """HWC column order -> the reference's CHW: the inverse of fc_columns_to_hwc (weights and gradients alike: a permutation)."""
+    return w.reshape(w.shape[0], size, size, channels).permute(0, 3, 1, 2).reshape(w.shape[0], -1)
 
 
 def foreground_rows(s: SolverCfg, cap: int, dev, aux, B: int) -> dict:

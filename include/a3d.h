@@ -35,7 +35,7 @@ int a3d_version(void);
 /* sizeof() of a descriptor struct, for bindings to verify their mirror of the layout.  id: 0 a3d_conv_desc, 1 a3d_rpn_desc,
  * 2 a3d_boxdet_desc, 3 a3d_roialign_desc, 4 a3d_paste_desc, 5 a3d_pack_desc, 6 a3d_wgrad_desc, 7 a3d_roialign_bwd_desc,
  * 8 a3d_match_desc, 9 a3d_rpn_loss_desc, 10 a3d_box_loss_desc, 11 a3d_roi_sample_desc, 12 a3d_sweep_desc, 13 a3d_transpose_item,
- * 14 a3d_axis_loss_desc, 15 a3d_mask_targets_desc, 16 a3d_mask_loss_desc; 0 for an unknown id. */
+ * 14 a3d_axis_loss_desc, 15 a3d_mask_targets_desc, 16 a3d_mask_loss_desc, 17 a3d_plane_loss_desc; 0 for an unknown id. */
 size_t a3d_struct_size(int id);
 
 /* ------------------------------------------------------------------------------------------------
@@ -596,6 +596,38 @@ typedef struct a3d_mask_loss_desc {
 } a3d_mask_loss_desc;
 size_t a3d_mask_loss_workspace_bytes(void);
 int a3d_mask_loss(const a3d_mask_loss_desc *d, void *stream);
+
+/* Plane-normal head's training step (the plane share of config/step3_plane.yaml; pkg/modeling/roi_heads/plane_head.py:80-82, :96-124),
+ * csrc/plane_train.hip.  a3d_plane_loss: the 1024 -> 3 predictor, F.normalize, plane_rcnn_loss and the backward pass of all three in ONE
+ * pass over the FC's activation h [rows, K] (after ReLU).  Rows are the compacted foreground ROIs [0, *live), *live clamped to
+ * [0, rows].  Per live row r with gt = gt_planes[row_img[r]][row_gt[r]]:
+ *   raw = w . h[r] + b,  pred = raw / max(|raw|, 1e-12),  t = gt / max(|gt|, 1e-12)   (normal_only == 0: pred = raw, t = gt),
+ *   loss = k sum |pred - t|,  k = loss_weight / *live  (an L1 SUM over rows and components divided by the ROW count),
+ *   draw = backward of the normalisation of k sign(pred - t)  (sign 0 at 0; below the eps clamp no tangential term passes),
+ *   dh[r] = (h[r] > 0) ? w^T draw : 0,  dw += draw x h[r],  db += draw.
+ * A row whose row_img / row_gt is out of range contributes nothing to the loss or to any gradient (its dh row is written as zeros) and
+ * still counts in the divisor.  h is read once and dh written once; dw, db and the loss leave through per-wave partials (workspace) and
+ * a second launch that sums them in a fixed order -- no atomics, the same bits on every run.  out = [dw (3K) | db (3) | loss].
+ * *live == 0: loss 0 and dw / db exactly 0.  Rows at or past *live are never read and their dh / raw never written.
+ * K % 256 == 0 (A3D_ERR_ARG otherwise; K > 1024: A3D_ERR_UNSUPPORTED); h, dh, w and workspace 16-byte aligned. */
+typedef struct a3d_plane_loss_desc {
+    const float *h;          /* [rows, K] */
+    const float *w;          /* [3, K] */
+    const float *b;          /* [3] */
+    const int *live;         /* DEVICE int */
+    const int *row_img;      /* [rows] */
+    const int *row_gt;       /* [rows] */
+    const float *gt_planes;  /* [B, max_gt, 3] */
+    float *workspace;        /* a3d_plane_loss_workspace_bytes(K) */
+    float *out;              /* [3K + 3 + 1]: dw | db | loss */
+    float *dh;               /* [rows, K] */
+    float *raw;              /* [rows, 3]: the predictor's output before the normalisation, or NULL */
+    int rows, K, B, max_gt;
+    float loss_weight;
+    int normal_only;
+} a3d_plane_loss_desc;
+size_t a3d_plane_loss_workspace_bytes(int K); /* 0 for a K the launch refuses as an argument error */
+int a3d_plane_loss(const a3d_plane_loss_desc *d, void *stream);
 
 /* Gradient of a3d_roi_align_fpn with respect to the pyramid: dfeat[level] += scatter(dout).  dfeat must hold the
  * gradient accumulated so far (or zeros).  Adaptive sampling (sampling_ratio 0) only: the box pooler. */
