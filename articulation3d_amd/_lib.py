@@ -160,6 +160,29 @@ class PlaneLossDesc(C.Structure):
     ]
 
 
+class BnTrainDesc(C.Structure):
+    _fields_ = [
+        ("z", fptr), ("gamma", fptr), ("beta", fptr), ("y", fptr), ("mean", fptr), ("invstd", fptr), ("var", fptr),
+        ("running_mean", fptr), ("running_var", fptr), ("dy", fptr), ("dz", fptr), ("dgamma", fptr), ("dbeta", fptr), ("workspace", fptr),
+        ("N", C.c_int), ("C", C.c_int), ("act", C.c_int), ("dy_pitch", C.c_int), ("dy_off", C.c_int),
+        ("eps", C.c_float), ("momentum", C.c_float), ("pad_", C.c_int),
+    ]
+
+
+class DepthLossDesc(C.Structure):
+    _fields_ = [
+        ("d", fptr), ("gt", fptr), ("dd", fptr), ("out", fptr), ("workspace", fptr),
+        ("B", C.c_int), ("h", C.c_int), ("w", C.c_int), ("loss_weight", C.c_float),
+    ]
+
+
+class PredBwdDesc(C.Structure):
+    _fields_ = [
+        ("x", fptr), ("g", fptr), ("w", fptr), ("dx", fptr), ("out", fptr), ("workspace", fptr),
+        ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int),
+    ]
+
+
 class TransposeItem(C.Structure):
     _fields_ = [("w", fptr), ("scale", fptr), ("wt", fptr), ("Cout", C.c_int), ("KH", C.c_int), ("KW", C.c_int), ("Cin", C.c_int),
                 ("block0", C.c_int), ("pad_", C.c_int)]
@@ -291,6 +314,15 @@ SIGNATURES = {
     "a3d_mask_loss": (C.c_int, [C.POINTER(MaskLossDesc), fptr]),
     "a3d_plane_loss_workspace_bytes": (C.c_size_t, [C.c_int]),
     "a3d_plane_loss": (C.c_int, [C.POINTER(PlaneLossDesc), fptr]),
+    "a3d_bn_train_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "a3d_bn_train_forward": (C.c_int, [C.POINTER(BnTrainDesc), fptr]),
+    "a3d_bn_train_backward": (C.c_int, [C.POINTER(BnTrainDesc), fptr]),
+    "a3d_depth_loss_workspace_bytes": (C.c_size_t, []),
+    "a3d_depth_loss": (C.c_int, [C.POINTER(DepthLossDesc), fptr]),
+    "a3d_pred_bwd_workspace_bytes": (C.c_size_t, []),
+    "a3d_depth_pred_backward": (C.c_int, [C.POINTER(PredBwdDesc), fptr]),
+    "a3d_ups2_concat": (C.c_int, [fptr, fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fptr]),
+    "a3d_resize_bilinear_backward_nhwc": (C.c_int, [fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fptr]),
     "a3d_roi_align_fpn_backward": (C.c_int, [C.POINTER(RoiAlignBwdDesc), fptr]),
     "a3d_roi_align_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(RoiAlignBwdDesc)]),
     "a3d_roi_align_fpn_backward_gather": (C.c_int, [C.POINTER(RoiAlignBwdDesc), fptr, fptr]),
@@ -313,7 +345,7 @@ SIGNATURES = {
 
 STRUCT_IDS = {0: ConvDesc, 1: RpnDesc, 2: BoxDetDesc, 3: RoiAlignDesc, 4: PasteDesc, 5: PackDesc, 6: WgradDesc,
               7: RoiAlignBwdDesc, 8: MatchDesc, 9: RpnLossDesc, 10: BoxLossDesc, 11: RoiSampleDesc, 12: SweepDesc, 13: TransposeItem,
-              14: AxisLossDesc, 15: MaskTargetsDesc, 16: MaskLossDesc, 17: PlaneLossDesc}
+              14: AxisLossDesc, 15: MaskTargetsDesc, 16: MaskLossDesc, 17: PlaneLossDesc, 18: BnTrainDesc, 19: DepthLossDesc, 20: PredBwdDesc}
 
 _lib = None
 

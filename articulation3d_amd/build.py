@@ -48,6 +48,7 @@ SOURCES = {
     "axis_train.hip": ["-ffp-contract=off"],  # normalise / double angle / smooth L1 round like the reference's separate operators
     "mask_train.hip": ["-ffp-contract=off"],  # mask-target sample coordinates round like the pooler's (the dot product asks for its FMAs)
     "plane_train.hip": ["-ffp-contract=off"],  # normalise / L1 round like the reference's separate operators (the dot products ask for their FMAs)
+    "depth_train.hip": ["-ffp-contract=off"],  # the bilinear weights and the L1 tail round like the reference's separate operators
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 COMMON += os.environ.get("A3D_HIPCC_FLAGS", "").split()  # developer builds only (e.g. -DA3D_ABLATIONS: timing-only kernel variants)

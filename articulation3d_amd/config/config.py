@@ -248,6 +248,7 @@ def get_cfg() -> CfgNode:
     _C.SOLVER.MOMENTUM = 0.9
     _C.SOLVER.NESTEROV = False
     _C.SOLVER.WEIGHT_DECAY = 0.0001
+    _C.SOLVER.WEIGHT_DECAY_NORM = 0.0
     _C.SOLVER.GAMMA = 0.1
     _C.SOLVER.STEPS = (30000,)
     _C.SOLVER.WARMUP_FACTOR = 0.001

@@ -191,6 +191,9 @@ extern "C" size_t a3d_struct_size(int id) {
         case 15: return sizeof(a3d_mask_targets_desc);
         case 16: return sizeof(a3d_mask_loss_desc);
         case 17: return sizeof(a3d_plane_loss_desc);
+        case 18: return sizeof(a3d_bn_train_desc);
+        case 19: return sizeof(a3d_depth_loss_desc);
+        case 20: return sizeof(a3d_pred_bwd_desc);
         default: return 0;
     }
 }

@@ -27,7 +27,7 @@ def solver_from_cfg(cfg) -> SolverCfg:
         roi_batch_per_image=m.ROI_HEADS.BATCH_SIZE_PER_IMAGE, roi_positive_fraction=m.ROI_HEADS.POSITIVE_FRACTION,
         roi_iou_threshold=float(m.ROI_HEADS.IOU_THRESHOLDS[0]), num_classes=m.ROI_HEADS.NUM_CLASSES,
         rpn_weights=tuple(m.RPN.BBOX_REG_WEIGHTS), box_weights=tuple(m.ROI_BOX_HEAD.BBOX_REG_WEIGHTS),
-        base_lr=s.BASE_LR, momentum=s.MOMENTUM, weight_decay=s.WEIGHT_DECAY, warmup_iters=s.WARMUP_ITERS,
+        base_lr=s.BASE_LR, momentum=s.MOMENTUM, weight_decay=s.WEIGHT_DECAY, weight_decay_norm=s.WEIGHT_DECAY_NORM, warmup_iters=s.WARMUP_ITERS,
         warmup_factor=s.WARMUP_FACTOR, steps=tuple(s.STEPS), gamma=s.GAMMA)
 
 
@@ -39,8 +39,9 @@ class FlatSGD:
 
     @property
     def param_groups(self):
-        return [{"lr": lr_at(self.trainer.iter, self.trainer.s), "momentum": self.trainer.s.momentum,
-                 "weight_decay": self.trainer.s.weight_decay}]
+        """One group per weight decay the trainer applies (the depth stage: the norm parameters' WEIGHT_DECAY_NORM beside WEIGHT_DECAY)."""
+        decays = getattr(self.trainer, "weight_decays", None) or [self.trainer.s.weight_decay]
+        return [{"lr": lr_at(self.trainer.iter, self.trainer.s), "momentum": self.trainer.s.momentum, "weight_decay": wd} for wd in decays]
 
     def zero_grad(self, set_to_none: bool = True):
         pass  # every step overwrites the flat gradient buffer

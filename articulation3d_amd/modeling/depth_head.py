@@ -90,7 +90,8 @@ class PlaneRCNNDepthHead(nn.Module):
     def forward(self, features, gt_depth=None):
         """Reference signature (planercnn.py:174): features dict (NCHW-shaped) -> pred_depth [N,480,640]."""
         if self.training:
-            raise NotImplementedError("depth loss (training) is outside the inference hot path (SURVEY.md 8f-1)")
+            raise NotImplementedError("the depth head trains through articulation3d_amd.training_depth.DepthTrainer (model(batched_inputs) in "
+                                      "training mode with configs/step3_depth.yaml); the module-level call has no training path")
         return self.forward_nhwc({k: to_nhwc(v) for k, v in features.items()})
 
 

@@ -41,10 +41,13 @@ STAGE3_FROZEN_HEADS = ("roi_heads.plane_head", "roi_heads.axis_head", "depth_hea
 # training stage 4 (the plane share of config/step3_plane.yaml): the same rule with the plane head trainable and the mask head off or frozen
 STAGE4_TRAINABLE = "roi_heads.plane_head"
 STAGE4_FROZEN_HEADS = ("roi_heads.mask_head", "roi_heads.axis_head", "depth_head")
+# training stage 5 (the depth share of config/step3_plane.yaml): the depth head trainable, every ROI head off or frozen
+STAGE5_TRAINABLE = "depth_head"
+STAGE5_FROZEN_HEADS = ("roi_heads.mask_head", "roi_heads.plane_head", "roi_heads.axis_head")
 # training stage -> (module, class) of its trainer, imported on first use.  Each class's static `batch_extras(batched_inputs)` gives the
-# ground truth its forward_backward takes after gt_classes: none, (gt_rot_axis, gt_tran_axis), (gt_masks,), (gt_planes,)
+# ground truth its forward_backward takes after gt_classes: none, (gt_rot_axis, gt_tran_axis), (gt_masks,), (gt_planes,), (gt_depth,)
 STAGE_TRAINER = {1: ("..training", "DetectorTrainer"), 2: ("..training_axis", "AxisTrainer"), 3: ("..training_mask", "MaskTrainer"),
-                 4: ("..training_plane", "PlaneTrainer")}
+                 4: ("..training_plane", "PlaneTrainer"), 5: ("..training_depth", "DepthTrainer")}
 
 
 @dataclass
@@ -282,8 +285,9 @@ class PlaneRCNN(nn.Module):
         (configs/step3_mask.yaml: MASK_ON with roi_heads.mask_head trainable, FREEZE covering the four detector modules, and each of the
         plane, axis and depth heads either off or frozen -- the reference skips a frozen head in training the same way) or 4, its PLANE
         SHARE (configs/step3_planehead.yaml: PLANE_ON with roi_heads.plane_head trainable, the same FREEZE rule with the mask head in the
-        plane head's place).  Anything else (step3_plane.yaml's own flags, which train the mask, plane and depth losses in one joint
-        step, among it) raises NotImplementedError."""
+        plane head's place) or 5, its DEPTH SHARE (configs/step3_depth.yaml: DEPTH_ON with depth_head trainable, the four detector
+        modules frozen, every ROI head off or frozen).  Anything else (step3_plane.yaml's own flags, which train the mask, plane and
+        depth losses in one joint step, among it) raises NotImplementedError."""
         rh = self.roi_heads
         mask, plane, axis = (bool(getattr(rh, n, False)) for n in ("mask_on", "plane_on", "axis_on"))
         others = self.depth_head_on or mask or plane
@@ -293,7 +297,8 @@ class PlaneRCNN(nn.Module):
         if not others and axis and set(self.STAGE2_FREEZE) <= frozen:
             return 2
         on = {"roi_heads.mask_head": mask, "roi_heads.plane_head": plane, "roi_heads.axis_head": axis, "depth_head": bool(self.depth_head_on)}
-        for stage, head, rest in ((3, STAGE3_TRAINABLE, STAGE3_FROZEN_HEADS), (4, STAGE4_TRAINABLE, STAGE4_FROZEN_HEADS)):
+        for stage, head, rest in ((3, STAGE3_TRAINABLE, STAGE3_FROZEN_HEADS), (4, STAGE4_TRAINABLE, STAGE4_FROZEN_HEADS),
+                                  (5, STAGE5_TRAINABLE, STAGE5_FROZEN_HEADS)):
             if on[head] and head not in frozen and set(self.STAGE2_FREEZE) <= frozen and all(not on[h] or h in frozen for h in rest):
                 return stage
         raise NotImplementedError("training is implemented for config/step1_bbox.yaml (MASK_ON / PLANE_ON / AXIS_ON / DEPTH_ON false), "
@@ -302,8 +307,10 @@ class PlaneRCNN(nn.Module):
                                   " trainable, FREEZE covering the detector and every other head that is on: " + str(list(STAGE3_FROZEN_HEADS)) +
                                   ") and its plane share (configs/step3_planehead.yaml: PLANE_ON true, " + STAGE4_TRAINABLE +
                                   " trainable, FREEZE covering the detector and " + str(list(STAGE4_FROZEN_HEADS)) +
-                                  "); step3_plane.yaml's own flags, which train the mask, plane and depth losses in one joint step, and the "
-                                  "depth loss are out of scope")
+                                  ") and its depth share (configs/step3_depth.yaml: DEPTH_ON true, " + STAGE5_TRAINABLE +
+                                  " trainable, FREEZE covering the detector and " + str(list(STAGE5_FROZEN_HEADS)) +
+                                  "); step3_plane.yaml's own flags, which train the mask, plane and depth losses in one joint step, "
+                                  "are out of scope")
 
     def trainer(self, solver=None, precision: str = "bf16x3"):
         """The hand-written training step behind the reference's training-mode call: created on first use (it copies every
@@ -324,11 +331,11 @@ class PlaneRCNN(nn.Module):
         planercnn.py:83-123): list of {"image": CHW uint8 BGR, "instances": Instances(gt_boxes, gt_classes)} -> the loss dict
         {loss_cls, loss_box_reg, loss_rpn_cls, loss_rpn_loc} (stage 2: + the axis losses; stage 3: Instances carry gt_masks, a
         structures.BitMasks or a [G,H,W] tensor, and the dict is {loss_cls, loss_box_reg, loss_mask}; stage 4: Instances carry gt_planes [G,3]
-        and the dict is {loss_cls, loss_box_reg, loss_plane}).  There is no autograd graph: the call runs forward AND backward
+        and the dict is {loss_cls, loss_box_reg, loss_plane}; stage 5: every input carries "depth", an [H, W] float map, and the dict is
+        {loss_cls, loss_box_reg, depth_loss}).  There is no autograd graph: the call runs forward AND backward
         (DetectorTrainer.forward_backward) and leaves the gradients of the summed loss in the trainer's flat buffer; the returned
         scalars accept `.backward()` so the reference's loop body stays as it is, and `engine.build_optimizer(cfg, model).step()`
-        applies the fused all-reduce + SGD launch.  Only the step1_bbox configuration (BASELINE configs[4]: box branch; mask /
-        plane / axis / depth heads off) has a training path."""
+        applies the fused all-reduce + SGD launch.  The configurations with a training path are those of `training_stage`."""
         cls = self._trainer_class()
         assert "instances" in batched_inputs[0], "training needs ground-truth instances (planercnn.py:84-85)"
         imgs = [x["image"] for x in batched_inputs]
@@ -338,7 +345,7 @@ class PlaneRCNN(nn.Module):
             frames = frames.round().clamp(0, 255).to(torch.uint8)  # (detectron2's mapper hands over uint8; tolerate float 0-255)
         gt_boxes = [x["instances"].gt_boxes.tensor.float() for x in batched_inputs]
         gt_classes = [x["instances"].gt_classes.long() for x in batched_inputs]
-        extra = cls.batch_extras(batched_inputs)  # (stage 3: polygon ground truth, stage 4: malformed gt_planes -- refused before anything is built or run)
+        extra = cls.batch_extras(batched_inputs)  # (stage 3: polygon ground truth, stage 4: malformed gt_planes, stage 5: malformed depth maps -- refused before anything is built or run)
         tr = self.trainer()
         losses, _aux = tr.forward_backward(frames, gt_boxes, gt_classes, *extra, exchange=True)  # (optimizer.step() finishes the exchange)
         names = list(losses)
@@ -348,7 +355,7 @@ class PlaneRCNN(nn.Module):
     def train(self, mode: bool = True):
         """Leaving training mode writes the trainer's parameters back into the modules (inference packs its weights from them)."""
         if not mode and getattr(self, "_trainer", None) is not None and self.training:
-            self.load_state_dict(self._trainer.export_state_dict(), strict=False)  # (stage 2 / 3 / 4: the axis / mask / plane head's entries only)
+            self.load_state_dict(self._trainer.export_state_dict(), strict=False)  # (stage 2 / 3 / 4 / 5: the axis / mask / plane / depth head's entries only; the depth head's include its norms' buffers)
         return super().train(mode)
 
     # batches up to this size run the depth decoder on a second HIP stream beside the ROI branch (0 disables: every kernel then runs alone)

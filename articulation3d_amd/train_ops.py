@@ -322,6 +322,114 @@ def plane_loss(h: torch.Tensor, w: torch.Tensor, b: torch.Tensor, live: torch.Te
     return out, dh
 
 
+# ------------------------------------------------------------------------------------------ depth head (csrc/depth_train.hip)
+def _bn_desc(z, gamma, mean, invstd, y, act, ws):
+    C_ = _req(z).shape[-1]
+    N = z.numel() // C_
+    d = _lib.BnTrainDesc()
+    d.z, d.gamma, d.y, d.mean, d.invstd = z.data_ptr(), _req(gamma).data_ptr(), _req(y).data_ptr(), _req(mean).data_ptr(), _req(invstd).data_ptr()
+    d.N, d.C, d.act = N, C_, int(act)
+    assert y.shape == z.shape and gamma.numel() == mean.numel() == invstd.numel() == C_
+    nbytes = _lib.lib().a3d_bn_train_workspace_bytes(N, C_)
+    if ws is None and nbytes:  # (a shape the library refuses gets no workspace: the launch call then says so)
+        ws = torch.empty(nbytes // 4, device=z.device, dtype=torch.float32)
+    d.workspace = _p(ws)
+    return d
+
+
+def bn_train_forward(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, act: int, eps: float = 1e-3, momentum: float = 0.01,
+                     running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None,
+                     y: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
+    """Training-mode BatchNorm2d + activation over z [..., C] (a3d_bn_train_forward): batch mean and biased variance per channel,
+    y = act(gamma (z - mean) / sqrt(var + eps) + beta), the running statistics updated in place (unbiased variance).
+    -> (y, mean, invstd, var); mean / invstd stay on the device for bn_train_backward."""
+    C_ = z.shape[-1]
+    if y is None:
+        y = torch.empty_like(z)
+    mean, invstd, var = (torch.empty(C_, device=z.device, dtype=torch.float32) for _ in range(3))
+    d = _bn_desc(z, gamma, mean, invstd, y, act, ws)
+    d.beta, d.var = _req(beta).data_ptr(), var.data_ptr()
+    d.running_mean, d.running_var = _p(running_mean), _p(running_var)
+    d.eps, d.momentum = float(eps), float(momentum)
+    _lib.check(_lib.lib().a3d_bn_train_forward(C.byref(d), _stream()), "a3d_bn_train_forward")
+    return y, mean, invstd, var
+
+
+def bn_train_backward(dy: torch.Tensor, z: torch.Tensor, y: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor, gamma: torch.Tensor, *,
+                      act: int, dgamma: torch.Tensor, dbeta: torch.Tensor, dy_off: int = 0, dz: Optional[torch.Tensor] = None,
+                      ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Backward of bn_train_forward (a3d_bn_train_backward): fills dgamma / dbeta [C] -> dz like z.  dy [..., P] with P >= C: the layer's
+    gradient is the channel slice [dy_off, dy_off + C) of every row (a half of a concatenated gradient needs no copy)."""
+    C_ = z.shape[-1]
+    if dz is None:
+        dz = torch.empty_like(z)
+    d = _bn_desc(z, gamma, mean, invstd, y, act, ws)
+    assert _req(dy).numel() // dy.shape[-1] == d.N and _req(dz).shape == z.shape and _req(dgamma).numel() == _req(dbeta).numel() == C_
+    d.dy, d.dz, d.dgamma, d.dbeta = dy.data_ptr(), dz.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr()
+    d.dy_pitch, d.dy_off = dy.shape[-1], int(dy_off)
+    _lib.check(_lib.lib().a3d_bn_train_backward(C.byref(d), _stream()), "a3d_bn_train_backward")
+    return dz
+
+
+def bn_train_bytes(N: int, Cc: int) -> tuple:
+    """Bytes (forward, backward) the batch-norm launches must move for N rows of Cc floats: forward z twice (statistics; the centred pass
+    re-reads a workgroup's own rows from cache) + y once; backward dy, z, y twice (sums, apply) + dz once."""
+    row = 4 * Cc
+    return 3 * N * row, 7 * N * row
+
+
+def depth_loss(d: torch.Tensor, gt: torch.Tensor, *, loss_weight: float = 1.0):
+    """The masked L1 depth loss on the x2 bilinear upsampling of d [B, h, w] against gt [B, 2h, 2w] (a3d_depth_loss).
+    -> (out [2] = loss | live pixel count, dd [B, h, w] the loss's gradient with respect to d)."""
+    B, h, w = _req(d).shape
+    assert tuple(_req(gt).shape) == (B, 2 * h, 2 * w), (d.shape, gt.shape)
+    dd, out = torch.empty_like(d), torch.empty(2, device=d.device, dtype=torch.float32)
+    ws = torch.empty(_lib.lib().a3d_depth_loss_workspace_bytes() // 4, device=d.device, dtype=torch.float32)
+    ds = _lib.DepthLossDesc()
+    ds.d, ds.gt, ds.dd, ds.out, ds.workspace = d.data_ptr(), gt.data_ptr(), dd.data_ptr(), out.data_ptr(), ws.data_ptr()
+    ds.B, ds.h, ds.w, ds.loss_weight = B, h, w, float(loss_weight)
+    _lib.check(_lib.lib().a3d_depth_loss(C.byref(ds), _stream()), "a3d_depth_loss")
+    return out, dd
+
+
+def depth_pred_backward(x: torch.Tensor, g: torch.Tensor, w: torch.Tensor, *, out: Optional[torch.Tensor] = None):
+    """Backward of ops.conv3x3_to1 (a3d_depth_pred_backward): x [B, H, W, 64], g [B, H, W], w [9, 64] tap-major.
+    -> (out [577] = dw tap-major | db, dx like x).  The reference's layout of dw is out[:576].view(1, 3, 3, 64).permute(0, 3, 1, 2)."""
+    B, H, W, Cc = _req(x).shape
+    assert tuple(_req(g).shape) == (B, H, W) and _req(w).numel() == 9 * Cc
+    if out is None:
+        out = torch.empty(9 * Cc + 1, device=x.device, dtype=torch.float32)
+    dx = torch.empty_like(x)
+    ws = torch.empty(_lib.lib().a3d_pred_bwd_workspace_bytes() // 4, device=x.device, dtype=torch.float32)
+    d = _lib.PredBwdDesc()
+    d.x, d.g, d.w, d.dx, d.out, d.workspace = x.data_ptr(), g.data_ptr(), w.data_ptr(), dx.data_ptr(), _req(out).data_ptr(), ws.data_ptr()
+    d.B, d.H, d.W, d.C = B, H, W, Cc
+    assert out.numel() == 9 * Cc + 1
+    _lib.check(_lib.lib().a3d_depth_pred_backward(C.byref(d), _stream()), "a3d_depth_pred_backward")
+    return out, dx
+
+
+def ups2_concat(a: torch.Tensor, b2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[b, 2y + i, 2x + j] = cat(a[b, y, x], b2[b, y, x]) (a3d_ups2_concat): the dense input of a deconv block's weight gradient."""
+    B, H, W, Ca = _req(a).shape
+    Cb = 0
+    if b2 is not None:
+        assert tuple(_req(b2).shape[:3]) == (B, H, W)
+        Cb = b2.shape[3]
+    out = torch.empty((B, 2 * H, 2 * W, Ca + Cb), device=a.device, dtype=torch.float32)
+    _lib.check(_lib.lib().a3d_ups2_concat(a.data_ptr(), _p(b2), out.data_ptr(), B, H, W, Ca, Cb, _stream()), "a3d_ups2_concat")
+    return out
+
+
+def resize_bilinear_backward(dy: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """Gradient of ops.resize_bilinear with respect to its input [B, H, W, C], given dy [B, Ho, Wo, C] (a3d_resize_bilinear_backward_nhwc)."""
+    B, Ho, Wo, Cc = _req(dy).shape
+    dx = torch.empty((B, H, W, Cc), device=dy.device, dtype=torch.float32)
+    _lib.check(_lib.lib().a3d_resize_bilinear_backward_nhwc(dy.data_ptr(), dx.data_ptr(), B, H, W, Cc, Ho, Wo, _stream()),
+               "a3d_resize_bilinear_backward_nhwc")
+    return dx
+
+
 def roi_align_fpn_backward(dfeats: Sequence[torch.Tensor], scales: Sequence[float], boxes: torch.Tensor, dout: torch.Tensor, *,
                            P: int, sampling_ratio: int, aligned: bool, count: Optional[torch.Tensor] = None,
                            row_offset: Optional[torch.Tensor] = None, scatter: bool = False) -> None:

@@ -70,6 +70,7 @@ class SolverCfg:
     base_lr: float = 0.001
     momentum: float = 0.9
     weight_decay: float = 1e-4
+    weight_decay_norm: float = 0.0  # detectron2's SOLVER.WEIGHT_DECAY_NORM: the decay of trainable norm parameters (the depth stage's gamma / beta)
     warmup_iters: int = 1000
     warmup_factor: float = 0.001
     steps: Tuple[int, ...] = (210000, 250000)

@@ -1,5 +1,5 @@
 """The scaffold every head trainer over the frozen detector shares (training_axis.AxisTrainer, training_mask.MaskTrainer,
-training_plane.PlaneTrainer).
+training_plane.PlaneTrainer; training_depth.DepthTrainer takes everything but the ROI prologue).
 
 `HeadTrainer` owns, once:
   * the frozen detector (a `DetectorTrainer` driven through `frozen_forward`: stage 1's launches, precision, storage and ROI sampling seed)
@@ -224,14 +224,7 @@ class HeadTrainer:
         (`_ground_truth`) before the `start` mark and the frozen forward pass, so a malformed batch is refused before anything runs."""
         s, B = self.s, frames_u8.shape[0]
         gt = self._ground_truth(frames_u8, gt_boxes, *gt)
-        self._mark("start")
-        self._grad_scale = 1.0  # (self.grads is this rank's own gradient until optimizer_step has exchanged it)
-        saved_sk, ops.BF16_SPLITK_AUTO = ops.BF16_SPLITK_AUTO, True
-        try:
-            self.det.iter = self.iter  # (the ROI sampling seed follows the step count, as in stage 1)
-            box_l, aux = self.det.frozen_forward(frames_u8, gt_boxes, gt_classes, samples)
-        finally:
-            ops.BF16_SPLITK_AUTO = saved_sk
+        box_l, aux = self._frozen_step(frames_u8, gt_boxes, gt_classes, samples)
         fgd = foreground_rows(s, self.cap, self.dev, aux, B)
         if samples is not None:  # (given index sets: host control flow is allowed here; the cap must hold)
             assert int((aux["roi_cls"][:, :] < s.num_classes).logical_and(
@@ -243,6 +236,26 @@ class HeadTrainer:
         live_px = (live * (P * P)).to(torch.int32)
         pooled = ops.roi_align_fpn([aux["feats"][n] for n in self.in_features], self.pool_scales, fgd["boxes"], fgd["count"], P,
                                    self.pool_ratio, self.pool_aligned, row_offset=fgd["row_offset"], rows=M)
+        self._begin_head(exchange)
+        losses = dict(box_l)
+        aux.update(fg=fgd, pooled=pooled)
+        self._head(losses, aux, fgd, live, live_px, pooled, gt)
+        return losses, aux
+
+    def _frozen_step(self, frames_u8, gt_boxes, gt_classes, samples):
+        """The `start` mark and the frozen detector's forward pass of a step (the ground truth has been checked and uploaded)."""
+        self._mark("start")
+        self._grad_scale = 1.0  # (self.grads is this rank's own gradient until optimizer_step has exchanged it)
+        saved_sk, ops.BF16_SPLITK_AUTO = ops.BF16_SPLITK_AUTO, True
+        try:
+            self.det.iter = self.iter  # (the ROI sampling seed follows the step count, as in stage 1)
+            return self.det.frozen_forward(frames_u8, gt_boxes, gt_classes, samples)
+        finally:
+            ops.BF16_SPLITK_AUTO = saved_sk
+
+    def _begin_head(self, exchange: bool):
+        """In front of the head's launches: the gradient exchange opens (exchange=True) and the data-gradient filters of the current
+        weights are made."""
         self._xchg_live = False
         if exchange and self.grad_overlap != "0":
             if self._xchg is None:
@@ -253,11 +266,7 @@ class HeadTrainer:
                 self._xchg_live = True
         if self._tbatch is None:
             self._tbatch = T.TransposeBatch([(ly.w, None, ly.wt, ly.rows, ly.k, ly.k, ly.cin) for ly in self.layers.values()], self.dev)
-        self._tbatch.run()  # the data-gradient filters of the current weights
-        losses = dict(box_l)
-        aux.update(fg=fgd, pooled=pooled)
-        self._head(losses, aux, fgd, live, live_px, pooled, gt)
-        return losses, aux
+        self._tbatch.run()
 
     def _segment_ready(self, i: int, stream):
         if self._xchg_live:
@@ -270,10 +279,14 @@ class HeadTrainer:
         else:
             scale = allreduce_gradients(self.grads, self.pg, payload=self.grad_payload)
         self._grad_scale = scale
-        T.sgd_momentum(self.params, self.grads, self.momentum, lr=lr_at(self.iter, s), momentum=s.momentum, weight_decay=s.weight_decay,
-                       grad_scale=scale, first=self.iter == 0)
+        self._sgd(lr_at(self.iter, s), scale)
         self._mark("exchange_sgd")
         self.iter += 1
+
+    def _sgd(self, lr: float, scale: float):
+        s = self.s
+        T.sgd_momentum(self.params, self.grads, self.momentum, lr=lr, momentum=s.momentum, weight_decay=s.weight_decay, grad_scale=scale,
+                       first=self.iter == 0)
 
     def step(self, frames_u8, gt_boxes, gt_classes, *gt, samples=None):
         losses, aux = self.forward_backward(frames_u8, gt_boxes, gt_classes, *gt, samples=samples, exchange=True)

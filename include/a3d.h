@@ -35,7 +35,8 @@ int a3d_version(void);
 /* sizeof() of a descriptor struct, for bindings to verify their mirror of the layout.  id: 0 a3d_conv_desc, 1 a3d_rpn_desc,
  * 2 a3d_boxdet_desc, 3 a3d_roialign_desc, 4 a3d_paste_desc, 5 a3d_pack_desc, 6 a3d_wgrad_desc, 7 a3d_roialign_bwd_desc,
  * 8 a3d_match_desc, 9 a3d_rpn_loss_desc, 10 a3d_box_loss_desc, 11 a3d_roi_sample_desc, 12 a3d_sweep_desc, 13 a3d_transpose_item,
- * 14 a3d_axis_loss_desc, 15 a3d_mask_targets_desc, 16 a3d_mask_loss_desc, 17 a3d_plane_loss_desc; 0 for an unknown id. */
+ * 14 a3d_axis_loss_desc, 15 a3d_mask_targets_desc, 16 a3d_mask_loss_desc, 17 a3d_plane_loss_desc,
+ * 18 a3d_bn_train_desc, 19 a3d_depth_loss_desc, 20 a3d_pred_bwd_desc; 0 for an unknown id. */
 size_t a3d_struct_size(int id);
 
 /* ------------------------------------------------------------------------------------------------
@@ -628,6 +629,82 @@ typedef struct a3d_plane_loss_desc {
 } a3d_plane_loss_desc;
 size_t a3d_plane_loss_workspace_bytes(int K); /* 0 for a K the launch refuses as an argument error */
 int a3d_plane_loss(const a3d_plane_loss_desc *d, void *stream);
+
+/* Depth head's training step (the depth share of config/step3_plane.yaml; pkg/modeling/depth_net/depth_head.py:32-46, :80-89 and its
+ * l1LossMask), csrc/depth_train.hip.  All tensors fp32 NHWC; no atomics, no host synchronisation: sums leave through per-workgroup
+ * partials that a later launch folds in a fixed order, so every call gives the same bits.
+ *
+ * Training-mode BatchNorm2d over z [N = B H W, C], C 64 or 128, N >= 2 (anything else: A3D_ERR_ARG before any launch).
+ * a3d_bn_train_forward (three launches): per workgroup (count, mean, M2 about that mean) over its rows, merged in partial order ->
+ *   mean, var (BIASED), invstd = 1 / sqrt(var + eps);  y = act(gamma (z - mean) invstd + beta), act A3D_ACT_RELU or A3D_ACT_LEAKY;
+ *   running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with the UNBIASED N / (N - 1) var (skipped when
+ *   both are NULL).  The variance is never formed as E[z^2] - E[z]^2.
+ * a3d_bn_train_backward (three launches: partial sums, their fold, apply): g = dy act'(y) (1 where y > 0, else 0 or 0.01),
+ *   xh = (z - mean) invstd;  dgamma = sum g xh,  dbeta = sum g,  dz = gamma invstd (g - dbeta / N - xh dgamma / N).
+ *   Row r of dy is read at dy + r dy_pitch + dy_off: a channel slice of a wider tensor (dy_pitch, dy_off multiples of 4).
+ * z, y, dy, dz, workspace 16-byte aligned. */
+typedef struct a3d_bn_train_desc {
+    const float *z;         /* [N, C] the conv's output */
+    const float *gamma;     /* [C] */
+    const float *beta;      /* [C] */
+    float *y;               /* [N, C]: forward output, backward input */
+    float *mean;            /* [C]: forward output, backward input */
+    float *invstd;          /* [C]: forward output, backward input */
+    float *var;             /* [C] forward output or NULL */
+    float *running_mean;    /* [C] updated in place by the forward call, or NULL */
+    float *running_var;     /* [C] */
+    const float *dy;        /* backward */
+    float *dz;              /* [N, C] backward */
+    float *dgamma;          /* [C] backward */
+    float *dbeta;           /* [C] backward */
+    float *workspace;       /* a3d_bn_train_workspace_bytes(N, C) */
+    int N, C, act, dy_pitch, dy_off;
+    float eps, momentum;
+    int pad_;
+} a3d_bn_train_desc;
+size_t a3d_bn_train_workspace_bytes(int N, int C); /* 0 for a shape the launches refuse */
+int a3d_bn_train_forward(const a3d_bn_train_desc *d, void *stream);
+int a3d_bn_train_backward(const a3d_bn_train_desc *d, void *stream);
+
+/* The masked L1 depth loss and its gradient with respect to the low-resolution prediction d [B, h, w] (depth_pred's output):
+ *   pred = bilinear x2 of d (align_corners false, the arithmetic of a3d_resize_bilinear_nhwc, never stored),  mask = gt > 1e-4,
+ *   out[0] = loss_weight sum |pred - gt| mask / max(sum mask, 1),  out[1] = sum mask,
+ *   dd = the gradient of out[0]: each low-resolution pixel GATHERS sign(pred - gt) mask times its bilinear weight over its up to 4 x 4
+ *   output pixels (sign 0 at a tie), then one more launch scales by loss_weight / max(sum mask, 1) from the device-side count.
+ * Everything masked out: loss 0, gradient 0. */
+typedef struct a3d_depth_loss_desc {
+    const float *d;    /* [B, h, w] */
+    const float *gt;   /* [B, 2h, 2w] */
+    float *dd;         /* [B, h, w] */
+    float *out;        /* [2]: loss | live pixel count */
+    float *workspace;  /* a3d_depth_loss_workspace_bytes() */
+    int B, h, w;
+    float loss_weight;
+} a3d_depth_loss_desc;
+size_t a3d_depth_loss_workspace_bytes(void);
+int a3d_depth_loss(const a3d_depth_loss_desc *d, void *stream);
+
+/* Backward of a3d_conv3x3_to1_nhwc (C = 64): x [B, H, W, 64], g [B, H, W] the gradient of its output, w [9, 64] (tap-major) ->
+ * dx [B, H, W, 64], out = [dw (9 x 64, tap-major) | db].  x read once, dx written once; dw / db through per-workgroup partials. */
+typedef struct a3d_pred_bwd_desc {
+    const float *x;
+    const float *g;
+    const float *w;
+    float *dx;
+    float *out;        /* [9 * 64 + 1] */
+    float *workspace;  /* a3d_pred_bwd_workspace_bytes() */
+    int B, H, W, C;
+} a3d_pred_bwd_desc;
+size_t a3d_pred_bwd_workspace_bytes(void);
+int a3d_depth_pred_backward(const a3d_pred_bwd_desc *d, void *stream);
+
+/* out[b, 2y + i, 2x + j, :] = cat(a[b, y, x, :], b2[b, y, x, :]), i, j in {0, 1}: the dense input of a deconv block's weight gradient
+ * (nearest x2 upsampling of the channel concat).  Ca, Cb multiples of 4. */
+int a3d_ups2_concat(const float *a, const float *b2, float *out, int B, int H, int W, int Ca, int Cb, void *stream);
+
+/* Gradient of a3d_resize_bilinear_nhwc with respect to its input: dx [B, H, W, C] = gather of dy [B, Ho, Wo, C] (every input pixel
+ * collects the output pixels that read it, in output order).  C % 4 == 0; meant for the decoder's one small resize. */
+int a3d_resize_bilinear_backward_nhwc(const float *dy, float *dx, int B, int H, int W, int C, int Ho, int Wo, void *stream);
 
 /* Gradient of a3d_roi_align_fpn with respect to the pyramid: dfeat[level] += scatter(dout).  dfeat must hold the
  * gradient accumulated so far (or zeros).  Adaptive sampling (sampling_ratio 0) only: the box pooler. */
