@@ -252,6 +252,27 @@ class SweepDesc(C.Structure):
     ]
 
 
+RENDER_MASK, RENDER_POLY = 0, 1
+
+
+class RenderLayer(C.Structure):
+    _fields_ = [("kind", C.c_int), ("alpha", C.c_int), ("color", C.c_ubyte * 4),
+                ("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int), ("y1", C.c_int), ("p0", C.c_int), ("p1", C.c_int)]
+
+
+class RenderPiece(C.Structure):
+    _fields_ = [("n", C.c_int), ("abc", (C.c_float * 3) * 4), ("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int), ("y1", C.c_int)]
+
+
+class RenderDesc(C.Structure):
+    _fields_ = [
+        ("frames", fptr), ("layer_off", fptr), ("layers", fptr), ("pieces", fptr), ("inst_off", fptr), ("inst_row", fptr),
+        ("normals", fptr), ("bits", fptr), ("out", fptr),
+        ("F", C.c_int), ("H", C.c_int), ("W", C.c_int), ("pitch", C.c_int), ("col", C.c_int),
+        ("n_layers", C.c_int), ("n_pieces", C.c_int), ("n_inst", C.c_int), ("n_masks", C.c_int), ("pad_", C.c_int),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/a3d.h declares
 SIGNATURES = {
     "a3d_version": (C.c_int, []),
@@ -337,6 +358,7 @@ SIGNATURES = {
     "a3d_masks_unpack_bits": (C.c_int, [fptr, fptr, C.c_int, C.c_int, C.c_int, fptr]),
     "a3d_project_hypotheses": (C.c_int, [C.POINTER(SweepDesc), fptr]),
     "a3d_mask_iou_matrix": (C.c_int, [fptr, fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr]),
+    "a3d_render_panels": (C.c_int, [C.POINTER(RenderDesc), fptr]),
     "a3d_sgd_momentum": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_sgd_momentum_bf16g": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_f32_to_bf16_scaled": (C.c_int, [fptr, fptr, C.c_size_t, C.c_float, fptr]),
@@ -345,7 +367,8 @@ SIGNATURES = {
 
 STRUCT_IDS = {0: ConvDesc, 1: RpnDesc, 2: BoxDetDesc, 3: RoiAlignDesc, 4: PasteDesc, 5: PackDesc, 6: WgradDesc,
               7: RoiAlignBwdDesc, 8: MatchDesc, 9: RpnLossDesc, 10: BoxLossDesc, 11: RoiSampleDesc, 12: SweepDesc, 13: TransposeItem,
-              14: AxisLossDesc, 15: MaskTargetsDesc, 16: MaskLossDesc, 17: PlaneLossDesc, 18: BnTrainDesc, 19: DepthLossDesc, 20: PredBwdDesc}
+              14: AxisLossDesc, 15: MaskTargetsDesc, 16: MaskLossDesc, 17: PlaneLossDesc, 18: BnTrainDesc, 19: DepthLossDesc, 20: PredBwdDesc,
+              21: RenderLayer, 22: RenderPiece, 23: RenderDesc}
 
 _lib = None
 

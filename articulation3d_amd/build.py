@@ -49,6 +49,7 @@ SOURCES = {
     "mask_train.hip": ["-ffp-contract=off"],  # mask-target sample coordinates round like the pooler's (the dot product asks for its FMAs)
     "plane_train.hip": ["-ffp-contract=off"],  # normalise / L1 round like the reference's separate operators (the dot products ask for their FMAs)
     "depth_train.hip": ["-ffp-contract=off"],  # the bilinear weights and the L1 tail round like the reference's separate operators
+    "render.hip": ["-ffp-contract=off"],  # a pixel is inside a half-plane iff (A*px + B*py) + C >= 0 as three rounded operations: the stated law
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 COMMON += os.environ.get("A3D_HIPCC_FLAGS", "").split()  # developer builds only (e.g. -DA3D_ABLATIONS: timing-only kernel variants)

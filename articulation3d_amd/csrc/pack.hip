@@ -194,6 +194,9 @@ extern "C" size_t a3d_struct_size(int id) {
         case 18: return sizeof(a3d_bn_train_desc);
         case 19: return sizeof(a3d_depth_loss_desc);
         case 20: return sizeof(a3d_pred_bwd_desc);
+        case 21: return sizeof(a3d_render_layer);
+        case 22: return sizeof(a3d_render_piece);
+        case 23: return sizeof(a3d_render_desc);
         default: return 0;
     }
 }

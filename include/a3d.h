@@ -862,6 +862,60 @@ int a3d_project_hypotheses(const a3d_sweep_desc *d, void *stream);
 int a3d_mask_iou_matrix(const unsigned int *target_bits /*[F,words]*/, const unsigned int *proj_bits /*[A,words]*/, float *iou, int F,
                         int A, int H, int W, void *stream);
 
+/* ================================================================================================
+ * The clip's visualisation panels (the reference's output.mp4 row, tools/inference.py:230-276): per frame a "seg" panel
+ * (the frame with box outlines and articulation-axis arrows blended over it) and a surface-normal panel, in one launch
+ * over tables the host builds once per clip (articulation3d_amd/render.py).  Everything is on the device.
+ *
+ * The law (held bit for bit by tests/render_ref.py):
+ *   seg panel     start from the frame's pixel; apply the frame's layers [layer_off[f], layer_off[f+1]) in table order.
+ *                 A layer covers a pixel at most once, however many of its pieces do; where it does, every channel
+ *                 becomes (old*(256-alpha) + color*alpha + 128) >> 8.
+ *                 MASK layer: covered = the mask bit.  POLY layer: covered = OR over its pieces; inside a piece iff
+ *                 e >= 0 for each of its n half-planes, px = x + 0.5f, py = y + 0.5f, e = (A*px + B*py) + C in fp32,
+ *                 in that order, no contraction.  The cull boxes (a layer's, a piece's) are supersets of the coverage and
+ *                 never change it.
+ *   normal panel  n = sum_i bit_i * normal_i (component-wise, fp32, the frame's instances [inst_off[f], inst_off[f+1]) in
+ *                 ascending order); v = (n + 1.0f) / 2.0f * 255.0f; byte = low 8 bits of v truncated toward zero to
+ *                 int32.  For v in [0, 256) and at most two overlapping masks that is get_normal_map (arti_vis.py:203-215:
+ *                 matmul of the 0/1 masks with F.normalize(plane), astype(uint8)); the wrap outside that range is this
+ *                 library's choice (numpy leaves the cast unspecified there).  Normals must be finite.
+ * Frame f's seg panel goes to out[f, :, col : col+W, :], its normal panel to out[f, :, col+W : col+2W, :].
+ * ============================================================================================== */
+#define A3D_RENDER_MASK 0
+#define A3D_RENDER_POLY 1
+#define A3D_RENDER_MAX_HALFPLANES 4
+typedef struct a3d_render_layer {
+    int kind;               /* A3D_RENDER_MASK | A3D_RENDER_POLY                                               */
+    int alpha;              /* 0 .. 256                                                                        */
+    unsigned char color[4]; /* R, G, B (in the frames' channel order), pad                                     */
+    int x0, y0, x1, y1;     /* cull box: the layer covers no pixel outside [x0,x1) x [y0,y1)                   */
+    int p0, p1;             /* MASK: p0 = row of `bits`;  POLY: pieces [p0, p1)                                */
+} a3d_render_layer;
+typedef struct a3d_render_piece {
+    int n;                  /* half-planes in use, 0 .. 4 (0 covers nothing)                                   */
+    float abc[A3D_RENDER_MAX_HALFPLANES][3]; /* (A, B, C): inside is e >= 0                                    */
+    int x0, y0, x1, y1;     /* the piece's own cull box, as the layer's: a superset of what the piece covers   */
+} a3d_render_piece;
+typedef struct a3d_render_desc {
+    const unsigned char *frames;    /* [F,H,W,3] uint8                                                         */
+    const int *layer_off;           /* [F+1] ascending offsets into `layers`                                   */
+    const a3d_render_layer *layers; /* [n_layers]                                                              */
+    const a3d_render_piece *pieces; /* [n_pieces]                                                              */
+    const int *inst_off;            /* [F+1] ascending offsets into inst_row / normals                         */
+    const int *inst_row;            /* [n_inst] row of `bits`                                                  */
+    const float *normals;           /* [n_inst,3] unit normals                                                 */
+    const unsigned int *bits;       /* [n_masks, ceil(H*W/32)]: bit i of word w = pixel 32w+i (row-major)       */
+    unsigned char *out;             /* [F,H,pitch,3] uint8                                                     */
+    int F, H, W, pitch, col;
+    int n_layers, n_pieces, n_inst, n_masks;
+    int pad_;
+} a3d_render_desc;
+/* A3D_ERR_ARG before any launch: F < 0, H or W < 1, col < 0, col + 2W > pitch, a negative count, or a null table with a
+ * non-zero count (frames / out / layer_off / inst_off with F > 0).  F == 0 is a no-op.  Table entries that point outside
+ * their tables (a layer range past n_layers, a piece past n_pieces, a mask row past n_masks) are skipped, never read. */
+int a3d_render_panels(const a3d_render_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,8 +15,11 @@ Input (this image has no video decoder: cv2 / imageio are absent, so .mp4 is ref
 The frames go to the GPU as they come from the reader (uint8 RGB, any size): the reference's `cv2.resize(im, (640, 480))` and
 BGR flip (:216-218) run on the device, fused with the normalisation in front of the stem (a3d_preprocess_resize_u8).
 Output: <output>/predictions.json -- per frame the optimised detections (bbox xyxy, score, class, plane, rotation /
-translation axis, RLE mask) and <output>/tracks.json (tracked planes, has_rot, consensus axis).  The 2-D / 3-D
-visualisations of the reference (imageio video, pytorch3d meshes) are out of scope.
+translation axis, RLE mask) and <output>/tracks.json (tracked planes, has_rot, consensus axis).
+`--vis png|npy` also writes the reference's 2-D visualisation, the four panels per frame of its output.mp4
+(`[opt seg | opt normal | raw seg | raw normal]`, [480, 2560, 3] uint8 RGB), rendered on the GPU (articulation3d_amd/render.py):
+<output>/vis/frame_%05d.png or one <output>/vis.npy.  There is no video encoder here, so no .mp4.  The 3-D visualisation of the
+reference (pytorch3d meshes) is out of scope.
 """
 from __future__ import annotations
 
@@ -83,6 +86,55 @@ def read_frames(path: str, lo: int = 0, hi: int = None) -> np.ndarray:
     return np.ascontiguousarray(frames)
 
 
+def snapshot_predictions(preds):
+    """The raw predictions as they are before the optimiser, for the visualisation's raw panels.  optimize_planes re-weights the
+    scores on copies and clones pred_rot_axis / pred_planes before it writes a track's consensus into them, but a translation
+    track's consensus axis is written into pred_tran_axis in place: the small per-detection fields are copied here, boxes and
+    masks (never written) are shared."""
+    from articulation3d_amd.structures import Instances
+
+    out = []
+    for p in preds:
+        q = Instances(p.image_size)
+        for f in ("scores", "pred_planes", "pred_rot_axis", "pred_tran_axis", "pred_classes"):
+            v = getattr(p, f)
+            setattr(q, f, v.clone() if isinstance(v, torch.Tensor) else np.copy(v))
+        q.pred_boxes, q.pred_masks = p.pred_boxes, p.pred_masks
+        out.append(q)
+    return out
+
+
+def write_visualisation(args, device, frames_rgb, raw_preds, opt_preds, chunk: int = 32):
+    """--vis: resize the clip's frames on the device in chunks of `chunk` source frames (the detector's own front end, uint8
+    output, 0.9 MB per resized frame kept on the device), then ONE render_clip over the whole clip: its buffers are pinned and
+    allocated once, and the four-panel rows are written as they come off the copy pipeline.  render_clip works in chunks of 8
+    frames: 3.7 MB per row, so 88 MB of pinned memory in its three host buffers."""
+    from articulation3d_amd import ops
+    from articulation3d_amd.render import render_clip
+
+    n = len(frames_rgb)
+    u8 = torch.empty((n, 480, 640, 3), dtype=torch.uint8, device=device)
+    for lo in range(0, n, chunk):
+        src = torch.from_numpy(np.ascontiguousarray(frames_rgb[lo:lo + chunk])).to(device)
+        u8[lo:lo + chunk] = ops.preprocess_resize_u8(src, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), want_u8=True)[1]  # resized, still RGB
+    if args.vis == "png":
+        from PIL import Image
+
+        os.makedirs(os.path.join(args.output, "vis"), exist_ok=True)
+    else:
+        whole = np.lib.format.open_memmap(os.path.join(args.output, "vis.npy"), mode="w+", dtype=np.uint8, shape=(n, 480, 4 * 640, 3))
+    at = 0
+    for rows in render_clip(u8, raw_preds, opt_preds, chunk=8, mask_alpha=args.mask_alpha, conf_threshold=args.conf_threshold):
+        if args.vis == "png":
+            for k, row in enumerate(rows):
+                Image.fromarray(row).save(os.path.join(args.output, "vis", "frame_%05d.png" % (at + k)))
+        else:
+            whole[at:at + len(rows)] = rows
+        at += len(rows)
+    if args.vis == "npy":
+        whole.flush()
+
+
 def main():
     random.seed(2020)
     np.random.seed(2020)
@@ -99,6 +151,12 @@ def main():
     ap.add_argument("--no-precision-audit", action="store_true",
                     help="skip the load-time audit of the default arithmetic (PlaneRCNN.audit_precision: every fp16x2 layer checked against its "
                          "bf16x3 evaluation on the clip's first frames; layers that leave the format's window are pinned to bf16x3)")
+    ap.add_argument("--vis", choices=("none", "png", "npy"), default="none",
+                    help="write the reference's four-panel visualisation row per frame (opt seg | opt normal | raw seg | raw normal), rendered on "
+                         "the GPU: png = <output>/vis/frame_%%05d.png, npy = one <output>/vis.npy [F,480,2560,3].  .mp4 is unavailable: there is "
+                         "no video encoder in this environment")
+    ap.add_argument("--mask-alpha", default=0.0, type=float,
+                    help="--vis: opacity of the instance masks on the seg panels (0 = none, as the reference draws them)")
     ap.add_argument("opts", nargs=argparse.REMAINDER, default=[], help="KEY VALUE config overrides, e.g. MODEL.DEVICE cuda:0")
     args = ap.parse_args()
 
@@ -174,6 +232,7 @@ def main():
             return
         frames_rgb = read_frames(args.input)  # the optimiser's sweeps look at the whole clip
     planes = track_planes(preds)
+    raw_preds = snapshot_predictions(preds) if args.vis != "none" else None
     opt_preds = optimize_planes(preds, planes, "3dc", frames=frames_rgb)
 
     out = []
@@ -191,6 +250,8 @@ def main():
               for cat, ts in planes.items()}
     with open(os.path.join(args.output, "tracks.json"), "w") as f:
         json.dump(tracks, f)
+    if args.vis != "none":
+        write_visualisation(args, model.device, frames_rgb, raw_preds, opt_preds)
     kept = sum(len(p.pred_boxes) for p in opt_preds)
     print(f"{len(frames_rgb)} frames, {kept} detections above {args.conf_threshold}, "
           f"{len(planes['rot'])} rotation / {len(planes['trans'])} translation tracks -> {args.output}")
