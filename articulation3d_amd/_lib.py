@@ -273,6 +273,20 @@ class RenderDesc(C.Structure):
     ]
 
 
+MESH_MAX_POSES = 16
+
+
+class MeshDesc(C.Structure):
+    _fields_ = [
+        ("bits", fptr), ("H", C.c_int), ("W", C.c_int), ("stride", C.c_int), ("invert", C.c_int),
+        ("normal", C.c_float * 3), ("offset", C.c_float),
+        ("focal", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+        ("pivot", C.c_float * 3), ("A", C.c_int),
+        ("xforms", fptr), ("flip_yz", C.c_int), ("cap_v", C.c_int), ("cap_f", C.c_int), ("pad_", C.c_int),
+        ("verts", fptr), ("uvs", fptr), ("faces", fptr), ("counts", fptr), ("workspace", fptr),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/a3d.h declares
 SIGNATURES = {
     "a3d_version": (C.c_int, []),
@@ -359,6 +373,8 @@ SIGNATURES = {
     "a3d_project_hypotheses": (C.c_int, [C.POINTER(SweepDesc), fptr]),
     "a3d_mask_iou_matrix": (C.c_int, [fptr, fptr, fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr]),
     "a3d_render_panels": (C.c_int, [C.POINTER(RenderDesc), fptr]),
+    "a3d_mesh_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "a3d_mesh_build": (C.c_int, [C.POINTER(MeshDesc), fptr]),
     "a3d_sgd_momentum": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_sgd_momentum_bf16g": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_f32_to_bf16_scaled": (C.c_int, [fptr, fptr, C.c_size_t, C.c_float, fptr]),
@@ -368,7 +384,7 @@ SIGNATURES = {
 STRUCT_IDS = {0: ConvDesc, 1: RpnDesc, 2: BoxDetDesc, 3: RoiAlignDesc, 4: PasteDesc, 5: PackDesc, 6: WgradDesc,
               7: RoiAlignBwdDesc, 8: MatchDesc, 9: RpnLossDesc, 10: BoxLossDesc, 11: RoiSampleDesc, 12: SweepDesc, 13: TransposeItem,
               14: AxisLossDesc, 15: MaskTargetsDesc, 16: MaskLossDesc, 17: PlaneLossDesc, 18: BnTrainDesc, 19: DepthLossDesc, 20: PredBwdDesc,
-              21: RenderLayer, 22: RenderPiece, 23: RenderDesc}
+              21: RenderLayer, 22: RenderPiece, 23: RenderDesc, 24: MeshDesc}
 
 _lib = None
 

@@ -197,6 +197,7 @@ extern "C" size_t a3d_struct_size(int id) {
         case 21: return sizeof(a3d_render_layer);
         case 22: return sizeof(a3d_render_piece);
         case 23: return sizeof(a3d_render_desc);
+        case 24: return sizeof(a3d_mesh_desc);
         default: return 0;
     }
 }

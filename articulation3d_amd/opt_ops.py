@@ -1,5 +1,5 @@
 """Host-side wrappers over the optimiser-sweep kernels of include/a3d.h: bit-packed masks,
-hypothesis projection, IoU matrix.  torch tensors carry device memory only."""
+hypothesis projection, IoU matrix; the panel renderer and the dense mesh builder.  torch tensors carry device memory only."""
 from __future__ import annotations
 
 import ctypes as C
@@ -82,3 +82,54 @@ def render_panels_tables(frames_u8: torch.Tensor, layer_off: torch.Tensor, layer
         raise ValueError("bit masks do not have ceil(H*W/32) words per row")
     _lib.check(_lib.lib().a3d_render_panels(C.byref(d), _stream()), "a3d_render_panels")
     return out
+
+
+def mesh_lattice(H: int, W: int, stride: int):
+    """(Lh, Lw, worst-case cap_v, worst-case cap_f) of a3d_mesh_build's lattice."""
+    Lh, Lw = (H + stride - 1) // stride, (W + stride - 1) // stride
+    return Lh, Lw, Lh * Lw, 2 * (Lh - 1) * (Lw - 1)
+
+
+def mesh_build_into(bits_row: torch.Tensor, H: int, W: int, normal: Sequence[float], offset: float, pivot: Sequence[float], xforms: torch.Tensor,
+                    verts: torch.Tensor, uvs: torch.Tensor, faces: torch.Tensor, counts: torch.Tensor, *, stride: int = 1, invert: bool = False,
+                    flip_yz: bool = False, focal: float, cx: float, cy: float) -> None:
+    """a3d_mesh_build into caller-owned buffers: verts [A,cap_v,3] fp32, uvs [cap_v,2] fp32, faces [cap_f,3] int32, counts [2] int32.  No
+    synchronisation: counts holds the true (n_verts, n_faces) once the stream gets there, rows past the capacities are never written."""
+    if _req(bits_row, torch.int32).dim() != 1 or bits_row.numel() != words_per_mask(H, W):
+        raise ValueError(f"bits_row {tuple(bits_row.shape)}: want one mask row of ceil(H*W/32) = {words_per_mask(H, W)} words")
+    A = _req(xforms).shape[0]
+    cap_v, cap_f = _req(uvs).shape[0], _req(faces, torch.int32).shape[0]
+    if xforms.dim() != 2 or xforms.shape[1] != 12 or not 1 <= A <= _lib.MESH_MAX_POSES:
+        raise ValueError(f"xforms {tuple(xforms.shape)}: want [A,12] with 1 <= A <= {_lib.MESH_MAX_POSES}")
+    if tuple(_req(verts).shape) != (A, cap_v, 3) or tuple(uvs.shape) != (cap_v, 2) or tuple(faces.shape) != (cap_f, 3) or _req(counts, torch.int32).numel() != 2:
+        raise ValueError("verts / uvs / faces / counts must be [A,cap_v,3] / [cap_v,2] / [cap_f,3] / [2]")
+    d = _lib.MeshDesc()
+    d.bits, d.H, d.W, d.stride, d.invert = _p(bits_row), H, W, int(stride), int(bool(invert))
+    for i in range(3):
+        d.normal[i], d.pivot[i] = float(normal[i]), float(pivot[i])
+    d.offset, d.focal, d.cx, d.cy = float(offset), float(focal), float(cx), float(cy)
+    d.A, d.xforms, d.flip_yz, d.cap_v, d.cap_f = A, _p(xforms), int(bool(flip_yz)), cap_v, cap_f
+    ws = torch.empty((max(int(_lib.lib().a3d_mesh_workspace_bytes(H, W, int(stride))), 4) + 3) // 4, device=bits_row.device, dtype=torch.int32)
+    d.verts, d.uvs, d.faces, d.counts, d.workspace = _p(verts), _p(uvs), _p(faces), _p(counts), _p(ws)
+    _lib.check(_lib.lib().a3d_mesh_build(C.byref(d), _stream()), "a3d_mesh_build")
+
+
+def build_mesh(bits_row: torch.Tensor, H: int, W: int, normal: Sequence[float], offset: float, pivot: Sequence[float], xforms: torch.Tensor, *,
+               stride: int = 1, invert: bool = False, flip_yz: bool = False, focal: float, cx: float, cy: float):
+    """The dense mesh of one bit-packed mask on its plane in the A poses of xforms [A,12] (include/a3d.h, a3d_mesh_build's law):
+    -> (verts [A,n,3] fp32, uvs [n,2] fp32, faces [m,3] int32) on the device.  Allocates the lattice's worst case, reads the two
+    counts once (the call's only synchronisation) and slices."""
+    if H < 1 or W < 1 or stride < 1:
+        raise ValueError(f"H, W, stride = {H}, {W}, {stride}: all must be >= 1")
+    _Lh, _Lw, cap_v, cap_f = mesh_lattice(H, W, int(stride))
+    dev, A = bits_row.device, xforms.shape[0]
+    verts = torch.empty((A, cap_v, 3), device=dev, dtype=torch.float32)
+    uvs = torch.empty((cap_v, 2), device=dev, dtype=torch.float32)
+    faces = torch.empty((cap_f, 3), device=dev, dtype=torch.int32)
+    counts = torch.empty(2, device=dev, dtype=torch.int32)
+    mesh_build_into(bits_row, H, W, normal, offset, pivot, xforms, verts, uvs, faces, counts, stride=stride, invert=invert, flip_yz=flip_yz,
+                    focal=focal, cx=cx, cy=cy)
+    n, m = (int(v) for v in counts.tolist())
+    if n > cap_v or m > cap_f:
+        raise RuntimeError(f"a3d_mesh_build counted {n} vertices / {m} faces, past the lattice's worst case {cap_v} / {cap_f}")
+    return verts[:, :n], uvs[:n], faces[:m]

@@ -36,7 +36,8 @@ int a3d_version(void);
  * 2 a3d_boxdet_desc, 3 a3d_roialign_desc, 4 a3d_paste_desc, 5 a3d_pack_desc, 6 a3d_wgrad_desc, 7 a3d_roialign_bwd_desc,
  * 8 a3d_match_desc, 9 a3d_rpn_loss_desc, 10 a3d_box_loss_desc, 11 a3d_roi_sample_desc, 12 a3d_sweep_desc, 13 a3d_transpose_item,
  * 14 a3d_axis_loss_desc, 15 a3d_mask_targets_desc, 16 a3d_mask_loss_desc, 17 a3d_plane_loss_desc,
- * 18 a3d_bn_train_desc, 19 a3d_depth_loss_desc, 20 a3d_pred_bwd_desc; 0 for an unknown id. */
+ * 18 a3d_bn_train_desc, 19 a3d_depth_loss_desc, 20 a3d_pred_bwd_desc, 21 a3d_render_layer, 22 a3d_render_piece,
+ * 23 a3d_render_desc, 24 a3d_mesh_desc; 0 for an unknown id. */
 size_t a3d_struct_size(int id);
 
 /* ------------------------------------------------------------------------------------------------
@@ -915,6 +916,56 @@ typedef struct a3d_render_desc {
  * non-zero count (frames / out / layer_off / inst_off with F > 0).  F == 0 is a no-op.  Table entries that point outside
  * their tables (a layer range past n_layers, a piece past n_pieces, a mask row past n_masks) are skipped, never read. */
 int a3d_render_panels(const a3d_render_desc *d, void *stream);
+
+/* ================================================================================================
+ * The dense mesh of one mask on its plane, in up to 16 rigid poses (the reference's --save-obj block, tools/inference.py:44-168,
+ * over get_single_image_mesh's reduce_size=False branch, pkg/utils/vis.py:579-600).  Everything is on the device; the call
+ * does no host synchronisation.  normal / offset / focal / cx / cy / pivot / xforms mean exactly what they mean in a3d_sweep_desc.
+ *
+ * The law (held bit for bit by tests/mesh_ref.py):
+ *   lattice   pixels (y, x) with y % stride == 0 and x % stride == 0; Lh = ceil(H/stride), Lw = ceil(W/stride).  A lattice pixel
+ *             is live iff its mask bit XOR invert is 1 (bit i of word w = pixel 32w+i, words = ceil(H*W/32)).  Bits at or past
+ *             H*W in the last word are never live, whatever they hold.
+ *   vertices  vertex k is the k-th live lattice pixel in row-major order; n_verts is their number.
+ *   position  in float64: rx = (x - cx)/focal, ry = (y - cy)/focal, den = n0*rx + n1*ry + n2, depth = offset/den;
+ *             p = ((float)(depth*rx), (float)(depth*ry), (float)depth).  Per pose a, in fp32, left to right, no contraction:
+ *             q = p - pivot, t_i = (m[3i]*qx + m[3i+1]*qy + m[3i+2]*qz) + pivot_i + m[9+i], m = xforms[a].  With flip_yz,
+ *             t_y and t_z are negated last (exact: the reference's --webvis matrix diag(1,-1,-1)).  verts[a, k, :] = t.
+ *   uv        uvs[k] = ((float)((double)x / W), (float)(1.0 + (-(double)y) / H)).
+ *   faces     0-based indices local to the mesh, in the row-major order of their first vertex.  For a live (y, x) with
+ *             y + stride < H and x + stride < W: first [v(y,x), v(y+s,x+s), v(y,x+s)] if (y,x+s) and (y+s,x+s) are live,
+ *             then [v(y,x), v(y+s,x), v(y+s,x+s)] if (y+s,x) and (y+s,x+s) are live (the reference's "upper right" /
+ *             "bottom left" pair and its winding).  n_faces is their number.
+ *   counts    counts[0] = n_verts, counts[1] = n_faces: the TRUE numbers even when they exceed cap_v / cap_f.  Nothing is
+ *             ever written at or past a capacity; rows past the counts are left untouched.
+ * Worst case for a lattice: cap_v = Lh*Lw, cap_f = 2*(Lh-1)*(Lw-1).  Non-finite vertices (a plane edge-on to a ray) are
+ * whatever IEEE gives.
+ * ============================================================================================== */
+#define A3D_MESH_MAX_POSES 16
+typedef struct a3d_mesh_desc {
+    const unsigned int *bits;  /* [ceil(H*W/32)] one bit-packed mask (a row of a3d_masks_pack_bits' output)            */
+    int H, W, stride, invert;  /* stride >= 1; invert 0 / 1                                                            */
+    float normal[3];           /* as a3d_sweep_desc                                                                    */
+    float offset;
+    double focal, cx, cy;
+    float pivot[3];
+    int A;                     /* poses, 1 .. A3D_MESH_MAX_POSES                                                       */
+    const float *xforms;       /* [A][12]: R (row-major 3x3) then t; point' = R (point - pivot) + pivot + t            */
+    int flip_yz;               /* 0 / 1                                                                                */
+    int cap_v, cap_f;          /* rows of verts (per pose) / uvs, rows of faces                                        */
+    int pad_;
+    float *verts;              /* [A, cap_v, 3]                                                                        */
+    float *uvs;                /* [cap_v, 2]                                                                           */
+    int *faces;                /* [cap_f, 3]                                                                           */
+    int *counts;               /* [2]                                                                                  */
+    void *workspace;           /* a3d_mesh_workspace_bytes bytes, 4-byte aligned; contents are scratch                  */
+} a3d_mesh_desc;
+/* 0 when H, W or stride is out of range. */
+size_t a3d_mesh_workspace_bytes(int H, int W, int stride);
+/* A3D_ERR_ARG before any launch: a null descriptor, bits / xforms / counts / workspace null, verts or uvs null with cap_v > 0,
+ * faces null with cap_f > 0, H or W < 1, stride < 1, H*W >= 2^30 (2*H*W faces must fit int32), A outside 1 .. 16, a negative
+ * capacity. */
+int a3d_mesh_build(const a3d_mesh_desc *d, void *stream);
 
 #ifdef __cplusplus
 }

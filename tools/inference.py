@@ -18,8 +18,10 @@ Output: <output>/predictions.json -- per frame the optimised detections (bbox xy
 translation axis, RLE mask) and <output>/tracks.json (tracked planes, has_rot, consensus axis).
 `--vis png|npy` also writes the reference's 2-D visualisation, the four panels per frame of its output.mp4
 (`[opt seg | opt normal | raw seg | raw normal]`, [480, 2560, 3] uint8 RGB), rendered on the GPU (articulation3d_amd/render.py):
-<output>/vis/frame_%05d.png or one <output>/vis.npy.  There is no video encoder here, so no .mp4.  The 3-D visualisation of the
-reference (pytorch3d meshes) is out of scope.
+<output>/vis/frame_%05d.png or one <output>/vis.npy.  There is no video encoder here, so no .mp4.
+`--save-obj` writes the reference's 3-D model (its save_obj_model, :44-168) for the frames of `--obj-frames`:
+<output>/frame_%04d/arti_pred.obj + .mtl + uv_maps/*.png -- the most confident articulated plane in its opened poses, two axis
+markers and the background, as dense meshes built on the GPU (articulation3d_amd/mesh.py states the departures).
 """
 from __future__ import annotations
 
@@ -135,9 +137,35 @@ def write_visualisation(args, device, frames_rgb, raw_preds, opt_preds, chunk: i
         whole.flush()
 
 
-def main():
-    random.seed(2020)
-    np.random.seed(2020)
+def write_obj_models(args, device, frames_rgb, opt_preds):
+    """--save-obj: one articulated model per requested frame (indices past the clip are dropped, as are frames without a usable
+    detection -- each with a line on stdout).  The frames are resized on the device as write_visualisation resizes them."""
+    from articulation3d_amd import ops
+    from articulation3d_amd.mesh import articulated_model, save_obj
+
+    wanted = [i for i in args.obj_frames if 0 <= i < len(opt_preds)]
+    written = 0
+    if wanted:
+        src = torch.from_numpy(np.ascontiguousarray(frames_rgb[wanted])).to(device)
+        u8 = ops.preprocess_resize_u8(src, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), want_u8=True)[1].cpu().numpy()  # resized, still RGB
+    for k, i in enumerate(wanted):
+        model = articulated_model(opt_preds[i], u8[k], axis_dir=args.axis_dir, stride=args.obj_stride, bkgd_stride=args.obj_bkgd_stride,
+                                  webvis=args.webvis, device=device)
+        if model is None:
+            print(f"save-obj: frame {i} has no articulated plane to export")
+            continue
+        folder = os.path.join(args.output, "frame_%04d" % i)
+        os.makedirs(folder, exist_ok=True)
+        save_obj(folder, "arti_pred", model)
+        written += 1
+    print(f"save-obj: {written} of {len(wanted)} requested frames exported" if written else "save-obj: no model exported (no frame with a detection)")
+
+
+def _frame_list(text: str):
+    return [int(v) for v in text.split(",") if v.strip()]
+
+
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Articulation prediction on a clip (MI355X).")
     ap.add_argument("--config", required=True)
     ap.add_argument("--input", required=True)
@@ -157,8 +185,22 @@ def main():
                          "no video encoder in this environment")
     ap.add_argument("--mask-alpha", default=0.0, type=float,
                     help="--vis: opacity of the instance masks on the seg panels (0 = none, as the reference draws them)")
+    ap.add_argument("--save-obj", action="store_true",
+                    help="write <output>/frame_%%04d/arti_pred.obj (+ .mtl, uv_maps/*.png) for the frames of --obj-frames: the most confident "
+                         "articulated plane in its opened poses, axis markers and background, meshes built on the GPU")
+    ap.add_argument("--obj-frames", default=[0, 30, 60, 89], type=_frame_list, help="--save-obj: comma list of frame indices (past the clip: dropped)")
+    ap.add_argument("--webvis", action="store_true", help="--save-obj: flip y and z for web model viewers")
+    ap.add_argument("--axis-dir", choices=("l", "r"), default="l", help="--save-obj: the side the plane opens to")
+    ap.add_argument("--obj-stride", default=2, type=int, help="--save-obj: pixel lattice of the object's mesh")
+    ap.add_argument("--obj-bkgd-stride", default=8, type=int, help="--save-obj: pixel lattice of the background's mesh")
     ap.add_argument("opts", nargs=argparse.REMAINDER, default=[], help="KEY VALUE config overrides, e.g. MODEL.DEVICE cuda:0")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    random.seed(2020)
+    np.random.seed(2020)
+    args = build_parser().parse_args()
 
     # one process per GPU under torchrun (frames sharded by pipeline.detect_clip, ONE all-gather of the records per clip):
     # rank / device / process group are set up before anything touches the GPU; rank 0 alone tracks, optimises and writes
@@ -252,6 +294,8 @@ def main():
         json.dump(tracks, f)
     if args.vis != "none":
         write_visualisation(args, model.device, frames_rgb, raw_preds, opt_preds)
+    if args.save_obj:
+        write_obj_models(args, model.device, frames_rgb, opt_preds)
     kept = sum(len(p.pred_boxes) for p in opt_preds)
     print(f"{len(frames_rgb)} frames, {kept} detections above {args.conf_threshold}, "
           f"{len(planes['rot'])} rotation / {len(planes['trans'])} translation tracks -> {args.output}")
