@@ -287,6 +287,30 @@ class MeshDesc(C.Structure):
     ]
 
 
+EVAL_DET_COLS, EVAL_GT_FCOLS, EVAL_GT_ICOLS, EVAL_MAX_GT, EVAL_MAX_CLASSES = 14, 7, 12, 64, 64
+
+
+class EvalMatchDesc(C.Structure):
+    _fields_ = [
+        ("det", fptr), ("gt_f", fptr), ("gt_i", fptr), ("det_off", fptr), ("gt_off", fptr),
+        ("det_off_host", C.POINTER(C.c_int)), ("gt_off_host", C.POINTER(C.c_int)),
+        ("I", C.c_int), ("N", C.c_int), ("M", C.c_int), ("img_h", C.c_int), ("img_w", C.c_int), ("pad_", C.c_int),
+        ("filter_iou", C.c_double), ("iou_thresh", C.c_double), ("normal_thresh", C.c_double),
+        ("gt_id", fptr), ("iou", fptr), ("ea", fptr), ("normal_err", fptr), ("rank", fptr), ("tp", fptr),
+    ]
+
+
+class EvalApDesc(C.Structure):
+    _fields_ = [
+        ("tp", fptr), ("seg_off_host", C.POINTER(C.c_int)), ("npos_host", C.POINTER(C.c_int)), ("C", C.c_int), ("pad_", C.c_int),
+        ("ap", fptr), ("n_entries", fptr),
+    ]
+
+
+class DepthL1Desc(C.Structure):
+    _fields_ = [("pred", fptr), ("gt", fptr), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("pad_", C.c_int), ("sum", fptr), ("count", fptr)]
+
+
 # name -> (restype, argtypes); every symbol include/a3d.h declares
 SIGNATURES = {
     "a3d_version": (C.c_int, []),
@@ -375,6 +399,9 @@ SIGNATURES = {
     "a3d_render_panels": (C.c_int, [C.POINTER(RenderDesc), fptr]),
     "a3d_mesh_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "a3d_mesh_build": (C.c_int, [C.POINTER(MeshDesc), fptr]),
+    "a3d_eval_match": (C.c_int, [C.POINTER(EvalMatchDesc), fptr]),
+    "a3d_eval_ap": (C.c_int, [C.POINTER(EvalApDesc), fptr]),
+    "a3d_depth_l1": (C.c_int, [C.POINTER(DepthL1Desc), fptr]),
     "a3d_sgd_momentum": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_sgd_momentum_bf16g": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_f32_to_bf16_scaled": (C.c_int, [fptr, fptr, C.c_size_t, C.c_float, fptr]),
@@ -384,7 +411,7 @@ SIGNATURES = {
 STRUCT_IDS = {0: ConvDesc, 1: RpnDesc, 2: BoxDetDesc, 3: RoiAlignDesc, 4: PasteDesc, 5: PackDesc, 6: WgradDesc,
               7: RoiAlignBwdDesc, 8: MatchDesc, 9: RpnLossDesc, 10: BoxLossDesc, 11: RoiSampleDesc, 12: SweepDesc, 13: TransposeItem,
               14: AxisLossDesc, 15: MaskTargetsDesc, 16: MaskLossDesc, 17: PlaneLossDesc, 18: BnTrainDesc, 19: DepthLossDesc, 20: PredBwdDesc,
-              21: RenderLayer, 22: RenderPiece, 23: RenderDesc, 24: MeshDesc}
+              21: RenderLayer, 22: RenderPiece, 23: RenderDesc, 24: MeshDesc, 25: EvalMatchDesc, 26: EvalApDesc, 27: DepthL1Desc}
 
 _lib = None
 

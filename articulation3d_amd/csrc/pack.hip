@@ -198,6 +198,9 @@ extern "C" size_t a3d_struct_size(int id) {
         case 22: return sizeof(a3d_render_piece);
         case 23: return sizeof(a3d_render_desc);
         case 24: return sizeof(a3d_mesh_desc);
+        case 25: return sizeof(a3d_eval_match_desc);
+        case 26: return sizeof(a3d_eval_ap_desc);
+        case 27: return sizeof(a3d_depth_l1_desc);
         default: return 0;
     }
 }

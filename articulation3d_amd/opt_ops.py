@@ -1,5 +1,6 @@
 """Host-side wrappers over the optimiser-sweep kernels of include/a3d.h: bit-packed masks,
-hypothesis projection, IoU matrix; the panel renderer and the dense mesh builder.  torch tensors carry device memory only."""
+hypothesis projection, IoU matrix; the panel renderer, the dense mesh builder and the evaluation launches.  torch tensors carry device
+memory only."""
 from __future__ import annotations
 
 import ctypes as C
@@ -133,3 +134,62 @@ def build_mesh(bits_row: torch.Tensor, H: int, W: int, normal: Sequence[float], 
     if n > cap_v or m > cap_f:
         raise RuntimeError(f"a3d_mesh_build counted {n} vertices / {m} faces, past the lattice's worst case {cap_v} / {cap_f}")
     return verts[:, :n], uvs[:n], faces[:m]
+
+
+def _host_ints(values) -> "C.Array":
+    return (C.c_int * len(values))(*[int(v) for v in values])
+
+
+def eval_match(det: torch.Tensor, det_off: Sequence[int], gt_f: torch.Tensor, gt_i: torch.Tensor, gt_off: Sequence[int], *, filter_iou: float = 0.7,
+               iou_thresh: float = 0.5, normal_thresh: float = 30.0, img_hw=(480, 640), gt_off_dev: torch.Tensor = None):
+    """a3d_eval_match (include/a3d.h): det [N,14] fp32, gt_f [M,7] fp32, gt_i [M,12] int32 on the device, det_off / gt_off the HOST
+    offsets [I+1] (validated by the library before the launch; their device copies are made here, gt_off_dev may supply the second).
+    -> dict gt_id int32, iou / ea / normal_err float64, rank int32, tp uint8, each [N] on the device.  No synchronisation."""
+    N, M, I = _req(det).shape[0], _req(gt_f).shape[0], len(det_off) - 1
+    if det.dim() != 2 or det.shape[1] != _lib.EVAL_DET_COLS or tuple(gt_f.shape) != (M, _lib.EVAL_GT_FCOLS) or tuple(_req(gt_i, torch.int32).shape) != (M, _lib.EVAL_GT_ICOLS):
+        raise ValueError(f"det {tuple(det.shape)} / gt_f {tuple(gt_f.shape)} / gt_i {tuple(gt_i.shape)}: want [N,14], [M,7], [M,12]")
+    if len(gt_off) != I + 1 or I < 0:
+        raise ValueError("det_off and gt_off must hold I + 1 offsets each")
+    dev = det.device
+    out = dict(gt_id=torch.empty(N, device=dev, dtype=torch.int32), iou=torch.empty(N, device=dev, dtype=torch.float64),
+               ea=torch.empty(N, device=dev, dtype=torch.float64), normal_err=torch.empty(N, device=dev, dtype=torch.float64),
+               rank=torch.empty(N, device=dev, dtype=torch.int32), tp=torch.empty(N, device=dev, dtype=torch.uint8))
+    h_det, h_gt = _host_ints(det_off), _host_ints(gt_off)
+    d_det = torch.tensor(list(det_off), dtype=torch.int32).to(dev)
+    d_gt = gt_off_dev if gt_off_dev is not None else torch.tensor(list(gt_off), dtype=torch.int32).to(dev)
+    d = _lib.EvalMatchDesc()
+    d.det, d.gt_f, d.gt_i, d.det_off, d.gt_off = _p(det), _p(gt_f), _p(gt_i), _p(d_det), _p(_req(d_gt, torch.int32))
+    d.det_off_host, d.gt_off_host = h_det, h_gt
+    d.I, d.N, d.M, d.img_h, d.img_w = I, N, M, int(img_hw[0]), int(img_hw[1])
+    d.filter_iou, d.iou_thresh, d.normal_thresh = float(filter_iou), float(iou_thresh), float(normal_thresh)
+    d.gt_id, d.iou, d.ea, d.normal_err, d.rank, d.tp = (_p(out[k]) for k in ("gt_id", "iou", "ea", "normal_err", "rank", "tp"))
+    _lib.check(_lib.lib().a3d_eval_match(C.byref(d), _stream()), "a3d_eval_match")
+    return out
+
+
+def eval_ap(tp_sorted: torch.Tensor, seg_off: Sequence[int], npos: Sequence[int]):
+    """a3d_eval_ap: tp_sorted uint8 [n] (per class, descending score), seg_off [C+1] and npos [C] on the host
+    -> (ap [4,C] float64, n_entries [C] int32) on the device."""
+    Cn = len(npos)
+    if len(seg_off) != Cn + 1 or not 1 <= Cn <= _lib.EVAL_MAX_CLASSES or _req(tp_sorted, torch.uint8).numel() != int(seg_off[-1]):
+        raise ValueError(f"seg_off {list(seg_off)} / npos {list(npos)} / {tp_sorted.numel()} entries: want C + 1 offsets ending at the entry count, 1 <= C <= {_lib.EVAL_MAX_CLASSES}")
+    ap = torch.empty((4, Cn), device=tp_sorted.device, dtype=torch.float64)
+    n_entries = torch.empty(Cn, device=tp_sorted.device, dtype=torch.int32)
+    h_off, h_npos = _host_ints(seg_off), _host_ints(npos)
+    d = _lib.EvalApDesc()
+    d.tp, d.seg_off_host, d.npos_host, d.C, d.ap, d.n_entries = _p(tp_sorted), h_off, h_npos, Cn, _p(ap), _p(n_entries)
+    _lib.check(_lib.lib().a3d_eval_ap(C.byref(d), _stream()), "a3d_eval_ap")
+    return ap, n_entries
+
+
+def depth_l1(pred: torch.Tensor, gt: torch.Tensor):
+    """a3d_depth_l1: pred, gt [B,H,W] fp32 -> (sum [B] float64 of |pred - gt| over gt > 1e-4, count [B] int32).  Reproducible bits."""
+    if _req(pred).dim() != 3 or tuple(_req(gt).shape) != tuple(pred.shape):
+        raise ValueError(f"pred {tuple(pred.shape)} / gt {tuple(gt.shape)}: want two [B,H,W] maps")
+    B, H, W = pred.shape
+    s = torch.empty(B, device=pred.device, dtype=torch.float64)
+    n = torch.empty(B, device=pred.device, dtype=torch.int32)
+    d = _lib.DepthL1Desc()
+    d.pred, d.gt, d.B, d.H, d.W, d.sum, d.count = _p(pred), _p(gt), B, H, W, _p(s), _p(n)
+    _lib.check(_lib.lib().a3d_depth_l1(C.byref(d), _stream()), "a3d_depth_l1")
+    return s, n

@@ -37,7 +37,7 @@ int a3d_version(void);
  * 8 a3d_match_desc, 9 a3d_rpn_loss_desc, 10 a3d_box_loss_desc, 11 a3d_roi_sample_desc, 12 a3d_sweep_desc, 13 a3d_transpose_item,
  * 14 a3d_axis_loss_desc, 15 a3d_mask_targets_desc, 16 a3d_mask_loss_desc, 17 a3d_plane_loss_desc,
  * 18 a3d_bn_train_desc, 19 a3d_depth_loss_desc, 20 a3d_pred_bwd_desc, 21 a3d_render_layer, 22 a3d_render_piece,
- * 23 a3d_render_desc, 24 a3d_mesh_desc; 0 for an unknown id. */
+ * 23 a3d_render_desc, 24 a3d_mesh_desc, 25 a3d_eval_match_desc, 26 a3d_eval_ap_desc, 27 a3d_depth_l1_desc; 0 for an unknown id. */
 size_t a3d_struct_size(int id);
 
 /* ------------------------------------------------------------------------------------------------
@@ -966,6 +966,91 @@ size_t a3d_mesh_workspace_bytes(int H, int W, int stride);
  * faces null with cap_f > 0, H or W < 1, stride < 1, H*W >= 2^30 (2*H*W faces must fit int32), A outside 1 .. 16, a negative
  * capacity. */
 int a3d_mesh_build(const a3d_mesh_desc *d, void *stream);
+
+/* ================================================================================================
+ * Evaluation: the reference's articulation AP (ArtiEvaluator -> evaluate_for_arti_axis, pkg/evaluation/arti_evaluation.py:262-665,
+ * over pkg/utils/metrics.py and pkg/utils/VOCap.py) and its depth_l1_dist (pkg/evaluation/scannet_evaluation.py:241-248), on the
+ * device: one launch matches every detection of every image, one launch turns the sorted true-positive bits into the AP table.
+ * The law is stated in numpy float64 by tests/eval_ref.py; articulation3d_amd/evaluation.py lists the departures from the reference.
+ *
+ * a3d_eval_match, per image i with detections [det_off[i], det_off[i+1]) and ground truths [gt_off[i], gt_off[i+1]):
+ *   line      of a detection, per kind (rot: (sin, cos, off) = det[9:12]; tran: (sin, cos) = det[12:14], off = 0).  In fp32:
+ *             cx = (x1 + x2) / 2, cy = (y1 + y2) / 2, p = off * 100, x = (p * cos) + cx, y = (p * sin) + cy.  Then float64:
+ *             sin == 0 -> (x, 0, x, H-1);  k = -(cos / sin);  k == 0 -> (0, y, W-1, y);  otherwise the candidates, in this order,
+ *             v = y - k*x in [0, H) -> (0, v);  v = (k*(W-1) + y) - k*x in [0, H) -> (W-1, v);  v = x - y/k in [0, W) -> (v, 0);
+ *             v = (x - y/k) + (H-1)/k in [0, W) -> (v, H-1);  the line is the first candidate and the first later one that differs
+ *             from it (the first again if none does), (0, 0, 1, 1) if there is no candidate.  Every coordinate is truncated toward 0.
+ *   iou       float64 from the fp32 boxes: area = (x2 - x1) * (y2 - y1), w = min(x2) - max(x1), h = min(y2) - max(y1), both clamped
+ *             at 0, inter = w * h, iou = inter > 0 ? inter / ((area_d + area_g) - inter) : 0.  A detection's ground truth is the
+ *             argmax (lowest index on ties); it is valid iff that iou > filter_iou.  No ground truth: not valid.
+ *   ea        against the ground truth's line of the ground truth's kind; 0 if that line is invalid, or either line has equal end
+ *             points.  angle(l) = x1 == x2 ? -pi/2 : atan((y1 - y2) / (x1 - x2));  d = |angle_p - angle_g|, d = min(d, pi - d),
+ *             sa = max(0, 1 - d*2/pi)^2;  c = sqrt(dy^2 + dx^2) of the two mid points / max(W, H), se = max(0, 1 - c)^2;  ea = sa*se.
+ *   normal    n = plane / max(|plane|, 1e-12) (plane = det[6:9]), dot = (n0*g0 + (-n2)*(-g1)) + n1*g2 with g the ground truth's raw
+ *             normal; err = acos(clamp(dot, -1, 1)) / pi * 180, or 180 if |g| > 1.1.
+ *   rank      the number of detections j of the image with score_j > score_d, or score_j == score_d and j < d.
+ *   tp        bit m (0 bbox, 1 bbox+axis, 2 bbox+normal, 3 bbox+normal+axis) is set iff the detection QUALIFIES for m -- valid, its
+ *             class equals its ground truth's, iou > iou_thresh, and ea > iou_thresh / err < normal_thresh where m names them -- and
+ *             no detection of lower rank qualifies for m with the same ground truth.
+ * Outputs for a detection that is not valid: gt_id -1, iou its best iou (0 without ground truths), ea 0, normal_err 180, tp 0.
+ * ============================================================================================== */
+#define A3D_EVAL_DET_COLS 14 /* the detection record's head (a3d_detections_pack): box 0:4, score 4, class 5, plane 6:9, rot 9:12, tran 12:14 */
+#define A3D_EVAL_GT_FCOLS 7  /* box xyxy 0:4, raw normal 4:7                                                                           */
+#define A3D_EVAL_GT_ICOLS 12 /* class 0, kind 1 (0 rot, 1 tran), rot line x1 y1 x2 y2 2:6, rot valid 6, tran line 7:11, tran valid 11 */
+#define A3D_EVAL_MAX_GT 64   /* ground truths per image                                                                                */
+#define A3D_EVAL_MAX_CLASSES 64
+typedef struct a3d_eval_match_desc {
+    const float *det;            /* [N, A3D_EVAL_DET_COLS] fp32                                                              */
+    const float *gt_f;           /* [M, A3D_EVAL_GT_FCOLS] fp32                                                              */
+    const int *gt_i;             /* [M, A3D_EVAL_GT_ICOLS] int32                                                             */
+    const int *det_off;          /* [I+1] device copy of det_off_host                                                        */
+    const int *gt_off;           /* [I+1] device copy of gt_off_host                                                         */
+    const int *det_off_host;     /* [I+1] HOST: 0 = off[0] <= off[1] <= ... <= off[I] = N; validated before the launch       */
+    const int *gt_off_host;      /* [I+1] HOST: likewise, ending at M, no image with more than A3D_EVAL_MAX_GT               */
+    int I, N, M;
+    int img_h, img_w;            /* the lines' image size (the reference's 480 x 640)                                        */
+    int pad_;
+    double filter_iou, iou_thresh, normal_thresh;
+    int *gt_id;                  /* [N] index within the image's ground truths, -1 when not valid                            */
+    double *iou, *ea, *normal_err; /* [N] each                                                                               */
+    int *rank;                   /* [N]                                                                                      */
+    unsigned char *tp;           /* [N]                                                                                      */
+} a3d_eval_match_desc;
+/* A3D_ERR_ARG before any launch: a null descriptor, I / N / M negative, img_h or img_w < 1, null host offsets with I > 0, offsets
+ * that do not start at 0, descend, or do not end at N / M, an image with more than 64 ground truths, a null device table that has
+ * rows, a null output with N > 0, a NaN threshold, I == 0 with N or M not 0.  I == 0 is a no-op.  The kernel clamps the device offsets to N / M: a device copy that differs
+ * from the validated host one gives wrong numbers, never a read or write outside the tables. */
+int a3d_eval_match(const a3d_eval_match_desc *d, void *stream);
+
+/* AP per (metric m, class c): the entries of class c are tp[seg_off[c] .. seg_off[c+1]), already in descending score order.  In
+ * float64: t_i / f_i the inclusive counts of set / clear bit m up to entry i, rec_i = t_i / npos[c], prec_i = t_i / (t_i + f_i),
+ * mpre_i = max(prec_j, j >= i), ap = sum over the entries where rec changes of (rec_i - rec_(i-1)) * mpre_i, rec_(-1) = 0 (VOCap.py's
+ * closing sentinel (1, 0) adds nothing).  ap[m*C + c]; 0 for a class without entries or with npos[c] <= 0.  n_entries[c] = the
+ * segment's length. */
+typedef struct a3d_eval_ap_desc {
+    const unsigned char *tp;     /* [seg_off[C]] true-positive bits, a3d_eval_match's tp gathered in sorted order             */
+    const int *seg_off_host;     /* [C+1] HOST, 0 first, ascending                                                           */
+    const int *npos_host;        /* [C] HOST: annotations of class c in the whole dataset                                    */
+    int C;                       /* 1 .. A3D_EVAL_MAX_CLASSES                                                                */
+    int pad_;
+    double *ap;                  /* [4, C]                                                                                   */
+    int *n_entries;              /* [C]                                                                                      */
+} a3d_eval_ap_desc;
+/* A3D_ERR_ARG before any launch: a null descriptor or host table, C outside 1 .. 64, offsets that do not start at 0 or descend,
+ * tp null with entries, a null output. */
+int a3d_eval_ap(const a3d_eval_ap_desc *d, void *stream);
+
+/* Per image b: sum[b] = sum over pixels of |pred - gt| * [gt > 1e-4] in float64, count[b] the number of such pixels.  One workgroup
+ * per image adds in a fixed order (no atomics): two runs give identical bits.  The caller's dataset value is the mean over images
+ * of sum / max(count, 1). */
+typedef struct a3d_depth_l1_desc {
+    const float *pred, *gt;      /* [B,H,W] fp32 each                                                                        */
+    int B, H, W, pad_;
+    double *sum;                 /* [B]                                                                                      */
+    int *count;                  /* [B]                                                                                      */
+} a3d_depth_l1_desc;
+/* A3D_ERR_ARG before any launch: a null descriptor, B < 0, H or W < 1, H*W >= 2^31, a null pointer with B > 0.  B == 0 is a no-op. */
+int a3d_depth_l1(const a3d_depth_l1_desc *d, void *stream);
 
 #ifdef __cplusplus
 }
