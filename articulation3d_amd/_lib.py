@@ -311,6 +311,30 @@ class DepthL1Desc(C.Structure):
     _fields_ = [("pred", fptr), ("gt", fptr), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("pad_", C.c_int), ("sum", fptr), ("count", fptr)]
 
 
+PLANE_GT_COLS = 8
+
+
+class EvalMaskCountsDesc(C.Structure):
+    _fields_ = [
+        ("det", fptr), ("gt", fptr), ("det_off", fptr), ("gt_off", fptr),
+        ("det_off_host", C.POINTER(C.c_int)), ("gt_off_host", C.POINTER(C.c_int)),
+        ("masks", fptr), ("det_slot", fptr), ("gt_bits", fptr),
+        ("I", C.c_int), ("N", C.c_int), ("M", C.c_int), ("S", C.c_int), ("H", C.c_int), ("W", C.c_int),
+        ("gt_id", fptr), ("inter", fptr), ("uni", fptr),
+    ]
+
+
+class EvalPlaneMatchDesc(C.Structure):
+    _fields_ = [
+        ("det", fptr), ("gt", fptr), ("det_off", fptr), ("gt_off", fptr),
+        ("det_off_host", C.POINTER(C.c_int)), ("gt_off_host", C.POINTER(C.c_int)),
+        ("inter", fptr), ("uni", fptr),
+        ("I", C.c_int), ("N", C.c_int), ("M", C.c_int), ("pad_", C.c_int),
+        ("iou_thresh", C.c_double), ("normal_thresh", C.c_double), ("offset_thresh", C.c_double),
+        ("gt_id", fptr), ("rank", fptr), ("box_iou", fptr), ("mask_iou", fptr), ("normal_err", fptr), ("offset_err", fptr), ("tp", fptr),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/a3d.h declares
 SIGNATURES = {
     "a3d_version": (C.c_int, []),
@@ -402,6 +426,8 @@ SIGNATURES = {
     "a3d_eval_match": (C.c_int, [C.POINTER(EvalMatchDesc), fptr]),
     "a3d_eval_ap": (C.c_int, [C.POINTER(EvalApDesc), fptr]),
     "a3d_depth_l1": (C.c_int, [C.POINTER(DepthL1Desc), fptr]),
+    "a3d_eval_mask_counts": (C.c_int, [C.POINTER(EvalMaskCountsDesc), fptr]),
+    "a3d_eval_plane_match": (C.c_int, [C.POINTER(EvalPlaneMatchDesc), fptr]),
     "a3d_sgd_momentum": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_sgd_momentum_bf16g": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_f32_to_bf16_scaled": (C.c_int, [fptr, fptr, C.c_size_t, C.c_float, fptr]),
@@ -411,7 +437,8 @@ SIGNATURES = {
 STRUCT_IDS = {0: ConvDesc, 1: RpnDesc, 2: BoxDetDesc, 3: RoiAlignDesc, 4: PasteDesc, 5: PackDesc, 6: WgradDesc,
               7: RoiAlignBwdDesc, 8: MatchDesc, 9: RpnLossDesc, 10: BoxLossDesc, 11: RoiSampleDesc, 12: SweepDesc, 13: TransposeItem,
               14: AxisLossDesc, 15: MaskTargetsDesc, 16: MaskLossDesc, 17: PlaneLossDesc, 18: BnTrainDesc, 19: DepthLossDesc, 20: PredBwdDesc,
-              21: RenderLayer, 22: RenderPiece, 23: RenderDesc, 24: MeshDesc, 25: EvalMatchDesc, 26: EvalApDesc, 27: DepthL1Desc}
+              21: RenderLayer, 22: RenderPiece, 23: RenderDesc, 24: MeshDesc, 25: EvalMatchDesc, 26: EvalApDesc, 27: DepthL1Desc,
+              28: EvalMaskCountsDesc, 29: EvalPlaneMatchDesc}
 
 _lib = None
 

@@ -10,8 +10,7 @@
 // workgroup per (class, metric), one workgroup per depth map.  No atomics on floats and no reduction whose order depends on timing:
 // the only atomic is an integer minimum in LDS, so every call gives the same bits.  Built with -ffp-contract=off: every operator
 // rounds on its own, as numpy's do.
-#include "a3d_common.h"
-#include "../../include/a3d.h"
+#include "eval_common.h"  // the box IoU, a detection's ground truth and rank: shared with csrc/plane_eval.hip
 
 #include <limits.h>
 
@@ -24,8 +23,6 @@ constexpr int DL1_THREADS = 1024;
 struct EvLine {
     double x1, y1, x2, y2;
 };
-
-__device__ __forceinline__ int ev_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // (sin, cos, offset / 100) about the box centre -> the line's two points on the image border (a3d.h: "line")
 __device__ EvLine ev_pred_line(const float *box, float s, float c, float off, int H, int W) {
@@ -94,16 +91,6 @@ __device__ double ev_normal_err(const float *plane, const float *gn) {
     return sqrt((g0 * g0 + g1 * g1) + g2 * g2) > 1.1 ? 180.0 : err;
 }
 
-__device__ __forceinline__ double ev_iou(const float *a, const float *b) {
-    const double ax1 = a[0], ay1 = a[1], ax2 = a[2], ay2 = a[3], bx1 = b[0], by1 = b[1], bx2 = b[2], by2 = b[3];
-    const double area_a = (ax2 - ax1) * (ay2 - ay1), area_b = (bx2 - bx1) * (by2 - by1);
-    double w = (ax2 < bx2 ? ax2 : bx2) - (ax1 > bx1 ? ax1 : bx1), h = (ay2 < by2 ? ay2 : by2) - (ay1 > by1 ? ay1 : by1);
-    w = w > 0.0 ? w : 0.0;
-    h = h > 0.0 ? h : 0.0;
-    const double inter = w * h;
-    return inter > 0.0 ? inter / ((area_a + area_b) - inter) : 0.0;
-}
-
 // One wave per image; its lanes loop over the image's detections.  best[m][g] = the lowest rank among the detections that qualify for
 // metric m with ground truth g: ranks are distinct within an image, so the minimum names one detection whatever the order of arrival.
 __global__ __launch_bounds__(A3D_WAVE) void eval_match_kernel(const a3d_eval_match_desc a) {
@@ -118,21 +105,9 @@ __global__ __launch_bounds__(A3D_WAVE) void eval_match_kernel(const a3d_eval_mat
     const double size = (double)max(a.img_w, a.img_h);
     for (int d = d0 + lane; d < d1; d += A3D_WAVE) {
         const float *row = a.det + (size_t)d * EV_DET;
-        const float sc = row[4];
-        int rank = 0;
-        for (int j = d0; j < d1; ++j) {
-            const float sj = a.det[(size_t)j * EV_DET + 4];
-            rank += (sj > sc || (sj == sc && j < d)) ? 1 : 0;
-        }
-        int gid = 0;
-        double biou = 0.0;
-        for (int g = 0; g < G; ++g) {
-            const double v = ev_iou(row, a.gt_f + (size_t)(g0 + g) * EV_GF);
-            if (g == 0 || v > biou) {
-                biou = v;
-                gid = g;
-            }
-        }
+        const int rank = ev_rank(a.det, d0, d1, d);
+        double biou;
+        const int gid = ev_best_gt(row, a.gt_f + (size_t)g0 * EV_GF, EV_GF, G, &biou);
         const bool valid = G > 0 && biou > a.filter_iou;
         double ea = 0.0, err = 180.0;
         unsigned q = 0;
@@ -287,14 +262,6 @@ __global__ __launch_bounds__(DL1_THREADS) void depth_l1_kernel(const a3d_depth_l
     }
 }
 
-bool ev_offsets_ok(const int *off, int I, int total, int max_per) {
-    if (!off || off[0] != 0 || off[I] != total) return false;
-    for (int i = 0; i < I; ++i) {
-        if (off[i + 1] < off[i]) return false;
-        if (max_per > 0 && off[i + 1] - off[i] > max_per) return false;
-    }
-    return true;
-}
 }  // namespace
 
 extern "C" int a3d_eval_match(const a3d_eval_match_desc *d, void *stream) {

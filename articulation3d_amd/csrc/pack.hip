@@ -201,6 +201,8 @@ extern "C" size_t a3d_struct_size(int id) {
         case 25: return sizeof(a3d_eval_match_desc);
         case 26: return sizeof(a3d_eval_ap_desc);
         case 27: return sizeof(a3d_depth_l1_desc);
+        case 28: return sizeof(a3d_eval_mask_counts_desc);
+        case 29: return sizeof(a3d_eval_plane_match_desc);
         default: return 0;
     }
 }

@@ -28,7 +28,8 @@ DEPARTURES from the reference, on purpose:
   * Score ties: within an image detections are ranked by (score descending, index); the AP entries are sorted by score with a STABLE
     sort over (image index in the ground-truth table, rank).  The reference's torch.sort is unstable and follows the order images were
     processed in; here the result does not depend on how the images were batched, sharded or ordered.
-  * Out of scope: COCO mAP (_eval_predictions), evaluate_for_recognition, mask IoU metrics, ScannetEvaluator, dataset registration.
+  * Out of scope: COCO mAP (_eval_predictions), evaluate_for_recognition, dataset registration.  The mask IoU metrics of the plane
+    stage (ScannetEvaluator -> evaluate_for_planes) are evaluation_planes.PlaneEvaluator, over the base class both share.
 """
 from __future__ import annotations
 
@@ -156,14 +157,9 @@ def record_normals(out) -> torch.Tensor:
     return ext[:, :R].contiguous()
 
 
-class ArtiEvaluator:
-    """The reference's ArtiEvaluator protocol -- reset / process / evaluate -- over an ArtiGroundTruth.  process() and
-    process_records() only queue device tensors (no host read of a detection); evaluate() reads the detection counts once."""
-
-    def __init__(self, gt: ArtiGroundTruth, filter_iou: float = 0.7, iou_thresh: float = 0.5, normal_threshold: float = 30.0):
-        self.gt = gt
-        self.filter_iou, self.iou_thresh, self.normal_threshold = float(filter_iou), float(iou_thresh), float(normal_threshold)
-        self.reset()
+class _EvaluatorBase:
+    """What ArtiEvaluator and evaluation_planes.PlaneEvaluator share: the image bookkeeping, the queue of detection rows and its
+    collection in the order of the ground-truth table, the depth rows and the gather.  `self.gt` carries index, device and __len__."""
 
     def reset(self):
         self._seen = set()
@@ -191,6 +187,92 @@ class ArtiEvaluator:
         if pred.shape != gt_depth.shape or pred.shape[0] != len(idx):
             raise ValueError(f"depth {tuple(pred.shape)} / ground-truth depth {tuple(gt_depth.shape)} for {len(idx)} images")
         self._depth.append((list(idx), *opt_ops.depth_l1(pred, gt_depth)))
+
+    # ------------------------------------------------------------------------------------------------------------------------------
+    def _pick(self):
+        """-> (pick: for every detection, in the order of the ground-truth table, its row in the queue's flattened rows -- int64
+        numpy --, det_off [I+1] numpy): the one host read of the counts."""
+        I = len(self.gt)
+        counted = [c for _, _, c in self._rows if c is not None]
+        counts = torch.cat(counted).tolist() if counted else []
+        per_image, base, k = {}, 0, 0
+        for idx, rows, c in self._rows:
+            if c is None:
+                per_image[idx[0]] = (base, rows.shape[0])
+                base += rows.shape[0]
+            else:
+                R = rows.shape[1]
+                for b, i in enumerate(idx):
+                    per_image[i] = (base + b * R, min(max(int(counts[k + b]), 0), R))
+                k += len(idx)
+                base += rows.shape[0] * R
+        det_off = np.zeros(I + 1, np.int64)
+        pick = []
+        for i in range(I):
+            b, n = per_image.get(i, (0, 0))
+            det_off[i + 1] = det_off[i] + n
+            pick.append(np.arange(b, b + n, dtype=np.int64))
+        return (np.concatenate(pick) if pick else np.zeros(0, np.int64)), det_off
+
+    def _collect(self):
+        """-> (det [N,14] in the order of the ground-truth table, det_off [I+1] numpy)."""
+        dev = self.gt.device
+        pick, det_off = self._pick()
+        if len(pick) == 0:
+            return torch.zeros((0, _lib.EVAL_DET_COLS), device=dev), det_off
+        flats = [rows.reshape(-1, _lib.EVAL_DET_COLS) for _, rows, _ in self._rows]
+        return torch.cat(flats)[torch.from_numpy(pick).to(dev)].contiguous(), det_off
+
+    def _gather(self, table: torch.Tensor, depth_rows: torch.Tensor):
+        """Under an initialised torch.distributed: every rank's compact rows to every rank through parallel.gather_records (counts,
+        then the live rows only).  The rows are fp32: image index, rank, score, class, valid, tp -- all exact in fp32 -- and the depth
+        rows of _depth_rows, which carry their float64 sums exactly."""
+        import torch.distributed as dist
+
+        from . import parallel
+
+        out = []
+        for rows in (table, depth_rows):
+            n = torch.tensor([rows.shape[0]], device="cpu" if dist.get_backend() == "gloo" else rows.device, dtype=torch.int64)
+            dist.all_reduce(n, op=dist.ReduceOp.MAX)  # one common slot count: gather_records clamps every rank's count to the local one
+            R = max(int(n.item()), 1)
+            block = rows.new_zeros((1, R, rows.shape[1]))
+            block[0, :rows.shape[0]] = rows
+            got, _cnt = parallel.gather_records_async(block, torch.tensor([rows.shape[0]], device=rows.device, dtype=torch.int32), rows=1).wait_compact()
+            out.append(got)
+        return out
+
+    def _depth_rows(self) -> torch.Tensor:
+        """[n,6] fp32: image index, the float64 sum as three fp32 terms (exact: 24 + 24 + 5 bits), the count as two 16-bit halves."""
+        dev = self.gt.device
+        if not self._depth:
+            return torch.zeros((0, 6), device=dev)
+        idx = torch.tensor([i for ids, _, _ in self._depth for i in ids], device=dev, dtype=torch.float32)
+        s = torch.cat([s for _, s, _ in self._depth])
+        c = torch.cat([c for _, _, c in self._depth]).long()
+        hi = s.float()
+        mid = (s - hi.double()).float()
+        lo = (s - hi.double() - mid.double()).float()
+        return torch.stack([idx, hi, mid, lo, (c >> 16).float(), (c & 0xFFFF).float()], 1)
+
+
+def _depth_l1_dist(depth_rows: torch.Tensor) -> float:
+    """depth_l1_dist from the (gathered) rows of _depth_rows: the mean over images, in image order, of sum / max(count, 1)."""
+    d = depth_rows.cpu().numpy()
+    order = np.argsort(d[:, 0], kind="stable")
+    sums = _join64(d[order, 1:4])
+    cnts = d[order, 4].astype(np.float64) * 65536.0 + d[order, 5].astype(np.float64)
+    return float(np.mean(sums / np.maximum(cnts, 1.0)))
+
+
+class ArtiEvaluator(_EvaluatorBase):
+    """The reference's ArtiEvaluator protocol -- reset / process / evaluate -- over an ArtiGroundTruth.  process() and
+    process_records() only queue device tensors (no host read of a detection); evaluate() reads the detection counts once."""
+
+    def __init__(self, gt: ArtiGroundTruth, filter_iou: float = 0.7, iou_thresh: float = 0.5, normal_threshold: float = 30.0):
+        self.gt = gt
+        self.filter_iou, self.iou_thresh, self.normal_threshold = float(filter_iou), float(iou_thresh), float(normal_threshold)
+        self.reset()
 
     def process(self, inputs: Sequence[Dict], outputs: Sequence[Dict]):
         """The reference's call shape (DatasetEvaluator.process): inputs[i]["image_id"]; outputs[i]["instances"] with pred_boxes,
@@ -240,55 +322,6 @@ class ArtiEvaluator:
         if depth is not None:
             self._score_depth(idx, depth, gt_depth)
 
-    # ------------------------------------------------------------------------------------------------------------------------------
-    def _collect(self):
-        """-> (det [N,14] in the order of the ground-truth table, det_off [I+1] numpy): the one host read of the counts."""
-        dev, I = self.gt.device, len(self.gt)
-        counted = [c for _, _, c in self._rows if c is not None]
-        counts = torch.cat(counted).tolist() if counted else []
-        per_image, flats, base, k = {}, [], 0, 0
-        for idx, rows, c in self._rows:
-            if c is None:
-                per_image[idx[0]] = (base, rows.shape[0])
-                flats.append(rows)
-                base += rows.shape[0]
-            else:
-                R = rows.shape[1]
-                for b, i in enumerate(idx):
-                    per_image[i] = (base + b * R, min(max(int(counts[k + b]), 0), R))
-                k += len(idx)
-                flats.append(rows.reshape(-1, _lib.EVAL_DET_COLS))
-                base += rows.shape[0] * R
-        det_off = np.zeros(I + 1, np.int64)
-        pick = []
-        for i in range(I):
-            b, n = per_image.get(i, (0, 0))
-            det_off[i + 1] = det_off[i] + n
-            pick.append(np.arange(b, b + n, dtype=np.int64))
-        pick = np.concatenate(pick) if pick else np.zeros(0, np.int64)
-        if len(pick) == 0:
-            return torch.zeros((0, _lib.EVAL_DET_COLS), device=dev), det_off
-        return torch.cat(flats)[torch.from_numpy(pick).to(dev)].contiguous(), det_off
-
-    def _gather(self, table: torch.Tensor, depth_rows: torch.Tensor):
-        """Under an initialised torch.distributed: every rank's compact rows to every rank through parallel.gather_records (counts,
-        then the live rows only).  The rows are fp32: image index, rank, score, class, valid, tp -- all exact in fp32 -- and the depth
-        rows of _depth_rows, which carry their float64 sums exactly."""
-        import torch.distributed as dist
-
-        from . import parallel
-
-        out = []
-        for rows in (table, depth_rows):
-            n = torch.tensor([rows.shape[0]], device="cpu" if dist.get_backend() == "gloo" else rows.device, dtype=torch.int64)
-            dist.all_reduce(n, op=dist.ReduceOp.MAX)  # one common slot count: gather_records clamps every rank's count to the local one
-            R = max(int(n.item()), 1)
-            block = rows.new_zeros((1, R, rows.shape[1]))
-            block[0, :rows.shape[0]] = rows
-            got, _cnt = parallel.gather_records_async(block, torch.tensor([rows.shape[0]], device=rows.device, dtype=torch.int32), rows=1).wait_compact()
-            out.append(got)
-        return out
-
     def evaluate(self) -> "OrderedDict[str, float]":
         """-> OrderedDict of "<metric> - <category name>" (classes with annotations only, as the reference logs them) and, when depth
         was processed, depth_l1_dist.  Afterwards `detections` holds this process' per-detection arrays (gt_id, iou, ea, normal_err,
@@ -330,25 +363,8 @@ class ArtiEvaluator:
                 for k, metric in enumerate(METRICS):
                     res[f"{metric} - {name}"] = float(ap[k, c])
         if len(depth_rows):
-            d = depth_rows.cpu().numpy()
-            order = np.argsort(d[:, 0], kind="stable")
-            sums = _join64(d[order, 1:4])
-            cnts = d[order, 4].astype(np.float64) * 65536.0 + d[order, 5].astype(np.float64)
-            res["depth_l1_dist"] = float(np.mean(sums / np.maximum(cnts, 1.0)))
+            res["depth_l1_dist"] = _depth_l1_dist(depth_rows)
         return res
-
-    def _depth_rows(self) -> torch.Tensor:
-        """[n,6] fp32: image index, the float64 sum as three fp32 terms (exact: 24 + 24 + 5 bits), the count as two 16-bit halves."""
-        dev = self.gt.device
-        if not self._depth:
-            return torch.zeros((0, 6), device=dev)
-        idx = torch.tensor([i for ids, _, _ in self._depth for i in ids], device=dev, dtype=torch.float32)
-        s = torch.cat([s for _, s, _ in self._depth])
-        c = torch.cat([c for _, _, c in self._depth]).long()
-        hi = s.float()
-        mid = (s - hi.double()).float()
-        lo = (s - hi.double() - mid.double()).float()
-        return torch.stack([idx, hi, mid, lo, (c >> 16).float(), (c & 0xFFFF).float()], 1)
 
 
 def _join64(parts: np.ndarray) -> np.ndarray:

@@ -193,3 +193,60 @@ def depth_l1(pred: torch.Tensor, gt: torch.Tensor):
     d.pred, d.gt, d.B, d.H, d.W, d.sum, d.count = _p(pred), _p(gt), B, H, W, _p(s), _p(n)
     _lib.check(_lib.lib().a3d_depth_l1(C.byref(d), _stream()), "a3d_depth_l1")
     return s, n
+
+
+def _plane_tables(det, det_off, gt, gt_off, gt_off_dev):
+    """The checks and offset tables a3d_eval_mask_counts and a3d_eval_plane_match share -> (N, M, I, host / device offsets)."""
+    N, M, I = _req(det).shape[0], _req(gt).shape[0], len(det_off) - 1
+    if det.dim() != 2 or det.shape[1] != _lib.EVAL_DET_COLS or tuple(gt.shape) != (M, _lib.PLANE_GT_COLS):
+        raise ValueError(f"det {tuple(det.shape)} / gt {tuple(gt.shape)}: want [N,{_lib.EVAL_DET_COLS}] and [M,{_lib.PLANE_GT_COLS}]")
+    if len(gt_off) != I + 1 or I < 0:
+        raise ValueError("det_off and gt_off must hold I + 1 offsets each")
+    d_det = torch.tensor(list(det_off), dtype=torch.int32).to(det.device)
+    d_gt = _req(gt_off_dev, torch.int32) if gt_off_dev is not None else torch.tensor(list(gt_off), dtype=torch.int32).to(det.device)
+    return N, M, I, _host_ints(det_off), _host_ints(gt_off), d_det, d_gt
+
+
+def eval_mask_counts(det: torch.Tensor, det_off: Sequence[int], gt: torch.Tensor, gt_off: Sequence[int], masks: torch.Tensor, det_slot: torch.Tensor,
+                     gt_bits: torch.Tensor, *, gt_off_dev: torch.Tensor = None):
+    """a3d_eval_mask_counts (include/a3d.h): det [N,14] fp32, gt [M,8] fp32, masks uint8 [S,H,W] as the detector wrote them, det_slot
+    int32 [N] (the row of `masks` of each detection; outside [0, S) = an empty mask), gt_bits int32 [M, ceil(H*W/32)] (pack_masks'
+    layout) on the device; det_off / gt_off the HOST offsets [I+1].  -> (gt_id, inter, uni), int32 [N] each.  No synchronisation."""
+    N, M, I, h_det, h_gt, d_det, d_gt = _plane_tables(det, det_off, gt, gt_off, gt_off_dev)
+    if _req(masks, torch.uint8).dim() != 3:
+        raise ValueError(f"masks {tuple(masks.shape)}: want uint8 [S,H,W]")
+    S, H, W = masks.shape
+    if H < 1 or W < 1:
+        raise ValueError(f"masks {tuple(masks.shape)}: H and W must be at least 1")
+    if tuple(_req(gt_bits, torch.int32).shape) != (M, words_per_mask(H, W)) or _req(det_slot, torch.int32).numel() != N:
+        raise ValueError(f"gt_bits {tuple(gt_bits.shape)} / det_slot {tuple(det_slot.shape)}: want [{M},{words_per_mask(H, W)}] and [{N}]")
+    out = tuple(torch.empty(N, device=det.device, dtype=torch.int32) for _ in range(3))
+    d = _lib.EvalMaskCountsDesc()
+    d.det, d.gt, d.det_off, d.gt_off, d.det_off_host, d.gt_off_host = _p(det), _p(gt), _p(d_det), _p(d_gt), h_det, h_gt
+    d.masks, d.det_slot, d.gt_bits = _p(masks), _p(det_slot), _p(gt_bits)
+    d.I, d.N, d.M, d.S, d.H, d.W = I, N, M, S, H, W
+    d.gt_id, d.inter, d.uni = (_p(t) for t in out)
+    _lib.check(_lib.lib().a3d_eval_mask_counts(C.byref(d), _stream()), "a3d_eval_mask_counts")
+    return out
+
+
+def eval_plane_match(det: torch.Tensor, det_off: Sequence[int], gt: torch.Tensor, gt_off: Sequence[int], inter: torch.Tensor, uni: torch.Tensor, *,
+                     iou_thresh: float = 0.5, normal_thresh: float = 30.0, offset_thresh: float = 0.3, gt_off_dev: torch.Tensor = None):
+    """a3d_eval_plane_match (include/a3d.h): det [N,14] fp32, gt [M,8] fp32, inter / uni int32 [N] (eval_mask_counts' columns) on the
+    device, det_off / gt_off the HOST offsets [I+1].  -> dict gt_id / rank int32, box_iou / mask_iou / normal_err / offset_err
+    float64, tp uint8, each [N] on the device.  No synchronisation."""
+    N, M, I, h_det, h_gt, d_det, d_gt = _plane_tables(det, det_off, gt, gt_off, gt_off_dev)
+    if _req(inter, torch.int32).numel() != N or _req(uni, torch.int32).numel() != N:
+        raise ValueError(f"inter {tuple(inter.shape)} / uni {tuple(uni.shape)}: want [{N}] each")
+    dev = det.device
+    i32, f64 = (lambda: torch.empty(N, device=dev, dtype=torch.int32)), (lambda: torch.empty(N, device=dev, dtype=torch.float64))
+    out = dict(gt_id=i32(), rank=i32(), box_iou=f64(), mask_iou=f64(), normal_err=f64(), offset_err=f64(), tp=torch.empty(N, device=dev, dtype=torch.uint8))
+    d = _lib.EvalPlaneMatchDesc()
+    d.det, d.gt, d.det_off, d.gt_off, d.det_off_host, d.gt_off_host = _p(det), _p(gt), _p(d_det), _p(d_gt), h_det, h_gt
+    d.inter, d.uni = _p(inter), _p(uni)
+    d.I, d.N, d.M = I, N, M
+    d.iou_thresh, d.normal_thresh, d.offset_thresh = float(iou_thresh), float(normal_thresh), float(offset_thresh)
+    for k, t in out.items():
+        setattr(d, k, _p(t))
+    _lib.check(_lib.lib().a3d_eval_plane_match(C.byref(d), _stream()), "a3d_eval_plane_match")
+    return out

@@ -37,7 +37,8 @@ int a3d_version(void);
  * 8 a3d_match_desc, 9 a3d_rpn_loss_desc, 10 a3d_box_loss_desc, 11 a3d_roi_sample_desc, 12 a3d_sweep_desc, 13 a3d_transpose_item,
  * 14 a3d_axis_loss_desc, 15 a3d_mask_targets_desc, 16 a3d_mask_loss_desc, 17 a3d_plane_loss_desc,
  * 18 a3d_bn_train_desc, 19 a3d_depth_loss_desc, 20 a3d_pred_bwd_desc, 21 a3d_render_layer, 22 a3d_render_piece,
- * 23 a3d_render_desc, 24 a3d_mesh_desc, 25 a3d_eval_match_desc, 26 a3d_eval_ap_desc, 27 a3d_depth_l1_desc; 0 for an unknown id. */
+ * 23 a3d_render_desc, 24 a3d_mesh_desc, 25 a3d_eval_match_desc, 26 a3d_eval_ap_desc, 27 a3d_depth_l1_desc,
+ * 28 a3d_eval_mask_counts_desc, 29 a3d_eval_plane_match_desc; 0 for an unknown id. */
 size_t a3d_struct_size(int id);
 
 /* ------------------------------------------------------------------------------------------------
@@ -1051,6 +1052,78 @@ typedef struct a3d_depth_l1_desc {
 } a3d_depth_l1_desc;
 /* A3D_ERR_ARG before any launch: a null descriptor, B < 0, H or W < 1, H*W >= 2^31, a null pointer with B > 0.  B == 0 is a no-op. */
 int a3d_depth_l1(const a3d_depth_l1_desc *d, void *stream);
+
+/* ================================================================================================
+ * Evaluation of the plane stage: the reference's ScanNet box / mask / plane AP and plane statistics (ScannetEvaluator ->
+ * evaluate_for_planes, pkg/evaluation/scannet_evaluation.py:254-450, over compare_planes of pkg/utils/metrics.py:6-19 and
+ * pkg/utils/VOCap.py).  Two launches (csrc/plane_eval.hip) in front of a3d_eval_ap, which is reused as it is.  The law is stated in
+ * numpy float64 by tests/plane_eval_ref.py; articulation3d_amd/evaluation_planes.py lists the departures from the reference.
+ *
+ * The ground truth is ONE fp32 table, A3D_PLANE_GT_COLS columns per row: box xyxy 0:4, plane (normal * offset) 4:7, class 7.
+ *
+ * a3d_eval_mask_counts, per detection n of image i (detections [det_off[i], det_off[i+1]), ground truths [gt_off[i], gt_off[i+1])):
+ *   g         the ground truth with the largest box IoU, by a3d_eval_match's law (float64 from the fp32 boxes, lowest index on ties;
+ *             one device function serves both); gt_id[n] = g, or -1 for an image without ground truth.
+ *   mask      row det_slot[n] of `masks` (uint8 [S,H,W], non-zero = set, read as the detector wrote it); a slot outside [0, S) is an
+ *             empty mask.
+ *   inter[n]  the number of pixels p < H*W that are set in the mask AND in row g of gt_bits (bit p & 31 of word p >> 5, the layout
+ *             of a3d_masks_pack_bits); 0 without ground truth.
+ *   uni[n]    the number of pixels p < H*W set in either; the mask's own area without ground truth.
+ * Bits of the last word at or past H*W are never read as pixels.  Integer sums only (integer atomics on counters the call zeroes
+ * first): the result does not depend on the order of arrival.  The work is spread over (detection, block of 16 384 pixels); a lane
+ * reads 16 mask bytes per load wherever the ADDRESS is 16-byte aligned -- a mask row starts at slot*H*W bytes, any alignment -- and
+ * the bytes before and after the aligned part of a block one by one.
+ *
+ * a3d_eval_plane_match, per image, one wave, in float64:
+ *   g, rank   as in a3d_eval_match; box_iou = the IoU with g.
+ *   mask_iou  uni > 0 ? inter / uni : 0 (two empty masks: 0).
+ *   planes    compare_planes: for p = det[6:9] and for the ground truth's plane, off = sqrt((p0*p0 + p1*p1) + p2*p2) + 1e-5,
+ *             n = p / off;  d = sqrt((dx*dx + dy*dy) + dz*dz) of n_p - n_g, clamped to [0, 2];
+ *             normal_err = 2 * asin(d / 2) / pi * 180;  offset_err = |off_p - off_g|.
+ *   tp        bit 0 box (box_iou > iou_thresh), bit 1 mask (mask_iou > iou_thresh), bit 2 plane (normal_err < normal_thresh and
+ *             offset_err < offset_thresh): set iff the detection QUALIFIES -- its class (det[5], truncated) equals its ground
+ *             truth's and the test holds -- and no detection of lower rank qualifies for the same bit with the same ground truth.
+ *             Bit 3 is always 0.  There is no filter_iou: every detection is an AP entry.
+ * An image without ground truth: gt_id -1, box_iou 0, mask_iou 0, normal_err 180, offset_err +inf, tp 0.
+ * ============================================================================================== */
+#define A3D_PLANE_GT_COLS 8
+typedef struct a3d_eval_mask_counts_desc {
+    const float *det;            /* [N, A3D_EVAL_DET_COLS] fp32 (only the box columns are read)                              */
+    const float *gt;             /* [M, A3D_PLANE_GT_COLS] fp32                                                              */
+    const int *det_off;          /* [I+1] device copy of det_off_host                                                        */
+    const int *gt_off;           /* [I+1] device copy of gt_off_host                                                         */
+    const int *det_off_host;     /* [I+1] HOST: 0 = off[0] <= off[1] <= ... <= off[I] = N; validated before the launch       */
+    const int *gt_off_host;      /* [I+1] HOST: likewise, ending at M, no image with more than A3D_EVAL_MAX_GT               */
+    const unsigned char *masks;  /* [S,H,W] uint8, non-zero = set                                                            */
+    const int *det_slot;         /* [N] the row of `masks` of detection n                                                    */
+    const unsigned int *gt_bits; /* [M, ceil(H*W/32)] a3d_masks_pack_bits' layout                                            */
+    int I, N, M, S, H, W;
+    int *gt_id, *inter, *uni;    /* [N] each                                                                                 */
+} a3d_eval_mask_counts_desc;
+/* A3D_ERR_ARG before any launch: a null descriptor, I / N / M / S negative, H or W < 1, H*W >= 2^31, null host offsets with I > 0,
+ * offsets that do not start at 0, descend, or do not end at N / M, an image with more than A3D_EVAL_MAX_GT ground truths, I == 0
+ * with N or M not 0, null device offsets, det_slot / det / an output null with N > 0, gt / gt_bits null with M > 0, masks null with
+ * S > 0.  I == 0 and N == 0 are no-ops.  The kernels clamp the device offsets to N / M, the slots to S and the ground truth to the
+ * image's range: wrong device tables give wrong numbers, never an access outside a buffer. */
+int a3d_eval_mask_counts(const a3d_eval_mask_counts_desc *d, void *stream);
+
+typedef struct a3d_eval_plane_match_desc {
+    const float *det;            /* [N, A3D_EVAL_DET_COLS] fp32                                                              */
+    const float *gt;             /* [M, A3D_PLANE_GT_COLS] fp32                                                              */
+    const int *det_off;          /* [I+1] device copy of det_off_host                                                        */
+    const int *gt_off;           /* [I+1] device copy of gt_off_host                                                         */
+    const int *det_off_host;     /* [I+1] HOST, validated as above                                                           */
+    const int *gt_off_host;      /* [I+1] HOST, validated as above                                                           */
+    const int *inter, *uni;      /* [N] each: a3d_eval_mask_counts' columns                                                  */
+    int I, N, M, pad_;
+    double iou_thresh, normal_thresh, offset_thresh;
+    int *gt_id, *rank;           /* [N] each                                                                                 */
+    double *box_iou, *mask_iou, *normal_err, *offset_err; /* [N] each                                                        */
+    unsigned char *tp;           /* [N]                                                                                      */
+} a3d_eval_plane_match_desc;
+/* A3D_ERR_ARG before any launch: as a3d_eval_mask_counts for the descriptor, the counts and the offsets; gt null with M > 0; det,
+ * inter, uni or an output null with N > 0; a NaN threshold.  I == 0 and N == 0 are no-ops.  The device offsets are clamped. */
+int a3d_eval_plane_match(const a3d_eval_plane_match_desc *d, void *stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,11 @@ synthetic dataset -> one JSON line.
   * ap_us: a3d_eval_ap over the valid detections' sorted true-positive bits, two classes;  sort_us: the three torch.sort calls
     and gathers that put the entries in order, for scale;
   * depth_us: a3d_depth_l1 over `--depth-batch` 480x640 maps, and the GB/s of the two maps it reads;
-  * evaluate_ms: ArtiEvaluator.evaluate() end to end on the same detections fed as packed records (wall time, host work included).
+  * evaluate_ms: ArtiEvaluator.evaluate() end to end on the same detections fed as packed records (wall time, host work included);
+  * mask_counts: a3d_eval_mask_counts (csrc/plane_eval.hip) on one detector batch -- `--mask-batch` images of `--dets` pasted
+    480x640 masks, `--mask-gts` ground truths each -- and, alternating with it in the same process, the route the library offered
+    before for the same numbers: opt_ops.pack_masks on the batch's masks, then mask_iou_matrix per image.  `--mask-rounds` rounds of
+    both; the medians, each route's spread over the rounds (max - min) and the new launch's GB/s from N*H*W + N*words*4 bytes.
 Needs a GPU: there is no fallback.
 """
 from __future__ import annotations
@@ -67,6 +71,58 @@ def timed(call, iters):
     return e0.elapsed_time(e1) * 1e3 / iters
 
 
+def bench_mask_counts(B: int, R: int, G: int, rounds: int, iters: int, H: int = 480, W: int = 640):
+    """-> dict: the new launch against pack_masks + mask_iou_matrix per image, alternating, on B x R masks with G ground truths each."""
+    from articulation3d_amd import opt_ops
+
+    dev = torch.device("cuda")
+    gen = torch.Generator(device=dev).manual_seed(7)
+
+    def boxes(n):
+        xy = torch.rand((n, 2), device=dev, generator=gen) * torch.tensor([W - 200.0, H - 160.0], device=dev)
+        wh = 60 + torch.rand((n, 2), device=dev, generator=gen) * torch.tensor([140.0, 100.0], device=dev)
+        return torch.cat([xy, xy + wh], 1)
+
+    def fill(b):  # [n,4] -> uint8 [n,H,W]: the box's rectangle, 255 inside as a pasted mask has it
+        yy, xx = torch.arange(H, device=dev)[None, :, None], torch.arange(W, device=dev)[None, None, :]
+        return (((xx >= b[:, 0, None, None]) & (xx < b[:, 2, None, None]) & (yy >= b[:, 1, None, None]) & (yy < b[:, 3, None, None])).to(torch.uint8) * 255).contiguous()
+
+    N, M = B * R, B * G
+    gbox = boxes(M)
+    src = (torch.arange(B, device=dev)[:, None] * G + torch.randint(0, G, (B, R), device=dev, generator=gen)).reshape(-1)
+    dbox = gbox[src] + (torch.rand((N, 4), device=dev, generator=gen) - 0.5) * 40
+    det = torch.zeros((N, 14), device=dev)
+    det[:, :4] = dbox
+    gt = torch.zeros((M, 8), device=dev)
+    gt[:, :4] = gbox
+    masks = torch.cat([fill(dbox[at:at + 100]) for at in range(0, N, 100)])
+    gt_bits = opt_ops.pack_masks(fill(gbox))
+    det_off, gt_off = [b * R for b in range(B + 1)], [b * G for b in range(B + 1)]
+    slot = torch.arange(N, device=dev, dtype=torch.int32)
+    words = opt_ops.words_per_mask(H, W)
+
+    new = lambda: opt_ops.eval_mask_counts(det, det_off, gt, gt_off, masks, slot, gt_bits)
+
+    def old():
+        bits = opt_ops.pack_masks(masks)
+        return [opt_ops.mask_iou_matrix(bits[b * R:(b + 1) * R], gt_bits[b * G:(b + 1) * G], H, W) for b in range(B)]
+
+    gt_id, inter, uni = new()
+    iou = torch.cat(old())  # [N,G] fp32: the column of each detection's ground truth is inter / uni
+    mine = torch.where(uni > 0, inter.double() / uni.double().clamp(min=1), torch.zeros((), device=dev, dtype=torch.float64))
+    assert float((iou.gather(1, gt_id.long()[:, None])[:, 0].double() - mine).abs().max()) < 1e-6
+    t_new, t_old = [], []
+    for _ in range(rounds):
+        t_new.append(timed(new, iters))
+        t_old.append(timed(old, iters))
+    med = lambda v: float(np.median(v))
+    nbytes = N * H * W + N * words * 4
+    return {"batch": B, "dets_per_image": R, "gts_per_image": G, "hw": [H, W], "rounds": rounds, "iters": iters,
+            "new_us": round(med(t_new), 1), "new_spread_us": round(max(t_new) - min(t_new), 1),
+            "pack_then_iou_us": round(med(t_old), 1), "pack_then_iou_spread_us": round(max(t_old) - min(t_old), 1),
+            "new_gbps": round(nbytes / med(t_new) / 1e3, 1), "mean_mask_iou": round(float(mine.mean()), 4)}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--images", type=int, default=5000)
@@ -74,6 +130,10 @@ def main():
     ap.add_argument("--gts", type=int, default=3)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--depth-batch", type=int, default=16)
+    ap.add_argument("--mask-batch", type=int, default=16)
+    ap.add_argument("--mask-gts", type=int, default=8)
+    ap.add_argument("--mask-rounds", type=int, default=7)
+    ap.add_argument("--mask-iters", type=int, default=10)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
@@ -122,6 +182,8 @@ def main():
     pred, gtd = torch.rand(B, 480, 640, device=dev) * 4, torch.rand(B, 480, 640, device=dev) * 4
     depth_us = timed(lambda: opt_ops.depth_l1(pred, gtd), args.iters)
 
+    mask_counts = bench_mask_counts(args.mask_batch, D, args.mask_gts, args.mask_rounds, args.mask_iters)
+
     gt = evaluation.ArtiGroundTruth(list(range(I)), gt_f, gt_i, gt_off, npos, ["arti_rot", "arti_tran"], ["arti_rot", "arti_tran"], dev)
     ev = evaluation.ArtiEvaluator(gt)
     step = 64
@@ -137,7 +199,7 @@ def main():
     print(json.dumps({"bench": "eval", "device": torch.cuda.get_device_name(0), "images": I, "dets_per_image": D, "gts_per_image": G,
                       "iters": args.iters, "valid_detections": int(valid.sum()), "match_us": round(match_us, 1), "match_call_us": round(match_call_us, 1), "sort_us": round(sort_us, 1),
                       "ap_us": round(ap_us, 1), "depth_batch": B, "depth_us": round(depth_us, 1),
-                      "depth_gbps": round(2 * B * 480 * 640 * 4 / depth_us / 1e3, 1), "evaluate_ms": round(evaluate_ms, 1),
+                      "depth_gbps": round(2 * B * 480 * 640 * 4 / depth_us / 1e3, 1), "evaluate_ms": round(evaluate_ms, 1), "mask_counts": mask_counts,
                       "ap": {k: round(v, 6) for k, v in res.items()}}))
 
 
