@@ -287,6 +287,7 @@ class MeshDesc(C.Structure):
     ]
 
 
+JPEG_BLOCK_BITS, JPEG_HUFF_VALS = 1658, 162
 EVAL_DET_COLS, EVAL_GT_FCOLS, EVAL_GT_ICOLS, EVAL_MAX_GT, EVAL_MAX_CLASSES = 14, 7, 12, 64, 64
 
 
@@ -428,6 +429,11 @@ SIGNATURES = {
     "a3d_depth_l1": (C.c_int, [C.POINTER(DepthL1Desc), fptr]),
     "a3d_eval_mask_counts": (C.c_int, [C.POINTER(EvalMaskCountsDesc), fptr]),
     "a3d_eval_plane_match": (C.c_int, [C.POINTER(EvalPlaneMatchDesc), fptr]),
+    "a3d_jpeg_tables": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "a3d_jpeg_quant": (C.c_int, [C.c_int, C.c_void_p]),
+    "a3d_jpeg_slot_bytes": (C.c_size_t, [C.c_int]),
+    "a3d_jpeg_encode": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr]),
+    "a3d_jpeg_pack": (C.c_int, [fptr, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, C.c_longlong, fptr]),
     "a3d_sgd_momentum": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_sgd_momentum_bf16g": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_f32_to_bf16_scaled": (C.c_int, [fptr, fptr, C.c_size_t, C.c_float, fptr]),

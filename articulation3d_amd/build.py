@@ -53,8 +53,9 @@ SOURCES = {
     "mesh.hip": ["-ffp-contract=off"],  # a vertex is (m0*qx + m1*qy + m2*qz) + pivot + t as separately rounded fp32 operations: the stated law, byte for byte
     "eval.hip": ["-ffp-contract=off"],  # IoU, line candidates and the normal's dot product round like tests/eval_ref.py's separate float64 operators
     "plane_eval.hip": ["-ffp-contract=off"],  # box IoU and compare_planes round like tests/plane_eval_ref.py's separate float64 operators
+    "jpeg.hip": [],  # integers only: nothing to contract
 }
-COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
+COMMON =["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 COMMON += os.environ.get("A3D_HIPCC_FLAGS", "").split()  # developer builds only (e.g. -DA3D_ABLATIONS: timing-only kernel variants)
 
 

@@ -250,3 +250,59 @@ def eval_plane_match(det: torch.Tensor, det_off: Sequence[int], gt: torch.Tensor
         setattr(d, k, _p(t))
     _lib.check(_lib.lib().a3d_eval_plane_match(C.byref(d), _stream()), "a3d_eval_plane_match")
     return out
+
+
+def jpeg_tables():
+    """The Annex K Huffman specifications the kernels are built with, as host bytes: (bits [4][16], vals [4][162]) in the order DC0, AC0,
+    DC1, AC1 -- what the headers of a stream must state."""
+    bits, vals = (C.c_ubyte * 64)(), (C.c_ubyte * (4 * _lib.JPEG_HUFF_VALS))()
+    _lib.check(_lib.lib().a3d_jpeg_tables(C.addressof(bits), C.addressof(vals)), "a3d_jpeg_tables")
+    return bytes(bits), bytes(vals)
+
+
+def jpeg_quant(quality: int) -> bytes:
+    """The two quantisation tables scaled for `quality` (1 .. 100): 2 x 64 bytes, natural order."""
+    out = (C.c_ubyte * 128)()
+    _lib.check(_lib.lib().a3d_jpeg_quant(int(quality), C.addressof(out)), "a3d_jpeg_quant")
+    return bytes(out)
+
+
+def jpeg_geometry(H: int, W: int):
+    """(segments per frame, MCUs per segment, bytes of a segment's slot) of a3d_jpeg_encode for H x W frames."""
+    slot = int(_lib.lib().a3d_jpeg_slot_bytes(int(W)))
+    if slot == 0 or not 1 <= H <= 65535:
+        raise ValueError(f"{H} x {W}: a JPEG is 1 .. 65535 pixels a side")
+    return (H + 7) // 8, (W + 7) // 8, slot
+
+
+def _pitched_frames(frames_u8: torch.Tensor):
+    """uint8 [F,H,W,3] on the device, dense or a column range of wider rows -> (F, H, W, pitch in pixels)."""
+    if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError(f"frames {tuple(frames_u8.shape)} {frames_u8.dtype}: want uint8 [F,H,W,3] on the device")
+    F_, H, W, _ = frames_u8.shape
+    s = frames_u8.stride()
+    if F_ and (s[3] != 1 or s[2] != 3 or s[1] % 3 or s[1] < 3 * W or (F_ > 1 and s[0] != H * s[1])):
+        raise ValueError(f"frames with strides {s}: want rows of `pitch` pixels, H rows per frame (a column range of a dense [F,H,pitch,3])")
+    return F_, H, W, (s[1] // 3 if F_ else W)
+
+
+def jpeg_encode_into(frames_u8: torch.Tensor, quality: int, coef: torch.Tensor, slots: torch.Tensor, seg_len: torch.Tensor, seg_off: torch.Tensor,
+                     frame_off: torch.Tensor) -> None:
+    """a3d_jpeg_encode into caller-owned buffers (no synchronisation): coef int16 with at least F*rows*mcus*192 elements, slots uint8 with at
+    least F*rows*slot bytes, seg_len / seg_off int32 [>= F*rows], frame_off int32 [>= F+1]."""
+    F_, H, W, pitch = _pitched_frames(frames_u8)
+    rows, mcus, slot = jpeg_geometry(H, W)
+    if (_req(coef, torch.int16).numel() < F_ * rows * mcus * 192 or _req(slots, torch.uint8).numel() < F_ * rows * slot
+            or _req(seg_len, torch.int32).numel() < F_ * rows or _req(seg_off, torch.int32).numel() < F_ * rows or _req(frame_off, torch.int32).numel() < F_ + 1):
+        raise ValueError("a buffer of a3d_jpeg_encode is smaller than the call needs")
+    _lib.check(_lib.lib().a3d_jpeg_encode(_p(frames_u8), F_, H, W, pitch, int(quality), _p(coef), _p(slots), _p(seg_len), _p(seg_off), _p(frame_off),
+                                          _stream()), "a3d_jpeg_encode")
+
+
+def jpeg_pack_into(slots: torch.Tensor, seg_off: torch.Tensor, seg_len: torch.Tensor, F_: int, H: int, W: int, packed: torch.Tensor) -> None:
+    """a3d_jpeg_pack: every segment to its place in `packed` (uint8, frame_off[F] bytes or more) with its RST marker behind it."""
+    rows, _mcus, slot = jpeg_geometry(H, W)
+    if _req(slots, torch.uint8).numel() < F_ * rows * slot or _req(seg_off, torch.int32).numel() < F_ * rows or _req(seg_len, torch.int32).numel() < F_ * rows:
+        raise ValueError("a buffer of a3d_jpeg_pack is smaller than the call needs")
+    _lib.check(_lib.lib().a3d_jpeg_pack(_p(slots), _p(seg_off), _p(seg_len), int(F_), H, W, _p(_req(packed, torch.uint8)), packed.numel(), _stream()),
+               "a3d_jpeg_pack")

@@ -1125,6 +1125,53 @@ typedef struct a3d_eval_plane_match_desc {
  * inter, uni or an output null with N > 0; a NaN threshold.  I == 0 and N == 0 are no-ops.  The device offsets are clamped. */
 int a3d_eval_plane_match(const a3d_eval_plane_match_desc *d, void *stream);
 
+/* ================================================================================================
+ * Motion-JPEG: the clip's visualisation rows as a video (the reference's output.mp4, tools/inference.py:254-276, is H.264 through
+ * imageio; this library writes baseline JPEG frames for an AVI container, articulation3d_amd/video.py).  Every frame is the entropy
+ * data of a JFIF image -- 8-bit, Y / Cb / Cr at 4:4:4, the Annex K tables of ITU-T T.81, a restart interval of one MCU row -- and
+ * the host puts the headers around it.  Integer arithmetic only.
+ *
+ * The law (held byte for byte by tests/mjpeg_ref.py, which tests/test_mjpeg_host.py holds to libjpeg):
+ *   geometry  rows = ceil(H/8) segments per frame, mcus = ceil(W/8) MCUs per segment, an MCU = one Y, one Cb, one Cr block.  The
+ *             pixel of a block at (y, x) past the image is the pixel at (min(y, H-1), min(x, W-1)).
+ *   colour    Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *             Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *             Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16      (>> arithmetic; libjpeg's constants and rounding)
+ *   DCT       X = component - 128;  T = (X C13' + 512) >> 10 over rows, F = (C13 T + 32768) >> 16 over columns,
+ *             C13[k][n] = rint(8192 a(k) cos((2n+1) k pi / 16)), a(0) = sqrt(1/8), a(k>0) = 1/2.  Every intermediate is within int32:
+ *             |X C13'| <= 128 * 23168, |T| <= 2896, |C13 T| <= 23168 * 2896 = 67 094 528.
+ *   quantise  q = sign(F) * ((|F| + (Q >> 1)) / Q);  Q = clamp((t * s + 50) / 100, 1, 255) of the Annex K value t,
+ *             s = quality < 50 ? 5000 / quality : 200 - 2 * quality  (libjpeg's jpeg_set_quality).  Coefficients travel in zigzag order.
+ *   entropy   per segment: the three DC predictors start at 0; Huffman symbols as in the standard (ZRL for runs over 15, EOB when a
+ *             block ends in zeros, one's complement amplitudes of negative values); the last byte is filled with 1-bits; every 0xFF
+ *             byte, the filled one included, is followed by 0x00.
+ *   stream    a frame's data is its segments in order with RSTm, m = row mod 8, behind every segment but the last; frame f's data
+ *             is packed[frame_off[f] .. frame_off[f+1]).
+ * A block is at most A3D_JPEG_BLOCK_BITS = 9 + 11 + 63 * (16 + 10) bits (|DC difference| <= 2040: category 11; |AC| < 1024: category
+ * 10), stuffing at most doubles a segment: a3d_jpeg_slot_bytes is that worst case, so no input can overrun a slot.  The result of a
+ * frame does not depend on F or on the frames beside it.
+ * ============================================================================================== */
+#define A3D_JPEG_BLOCK_BITS 1658
+#define A3D_JPEG_HUFF_VALS 162
+/* HOST tables, for the headers: bits [4][16] and vals [4][A3D_JPEG_HUFF_VALS] (zero-filled past a table's symbols), the Annex K Huffman
+ * specifications in the order DC0, AC0, DC1, AC1. */
+int a3d_jpeg_tables(unsigned char *bits, unsigned char *vals);
+/* HOST: out [2][64] = the two tables scaled for `quality`, natural order.  A3D_ERR_ARG outside 1 .. 100. */
+int a3d_jpeg_quant(int quality, unsigned char *out);
+/* Bytes of one segment's slot for frames W wide (a multiple of 16); 0 for W outside 1 .. 65535. */
+size_t a3d_jpeg_slot_bytes(int W);
+/* frames uint8 [F,H,pitch,3] RGB (pitch >= W pixels per row, so a view into wider rows works) -> seg_len [F*rows] the bytes of every
+ * segment, written at slots + s * slot_bytes; seg_off [F*rows] its place in the packed stream; frame_off [F+1].  coef (16-byte
+ * aligned, F * rows * mcus * 192 int16) is scratch.  Three launches, no synchronisation.  A3D_ERR_ARG before any launch: F < 0, H or W outside
+ * 1 .. 65535, pitch < W, quality outside 1 .. 100, a null pointer (frame_off always; the others with F > 0), a misaligned coef, or
+ * F * rows * (slot_bytes + 2) above 2^31 - 1 (the offsets are int32: encode fewer frames per call). */
+int a3d_jpeg_encode(const unsigned char *frames, int F, int H, int W, int pitch, int quality, short *coef, unsigned char *slots,
+                    int *seg_len, int *seg_off, int *frame_off, void *stream);
+/* Copies every segment to packed + seg_off[s] and puts its RST marker behind it.  packed_bytes is the size of the destination (the
+ * host reads frame_off[F] first): a segment that would end past it is left out, never written.  F == 0 is a no-op. */
+int a3d_jpeg_pack(const unsigned char *slots, const int *seg_off, const int *seg_len, int F, int H, int W, unsigned char *packed,
+                  long long packed_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,9 +16,11 @@ The frames go to the GPU as they come from the reader (uint8 RGB, any size): the
 BGR flip (:216-218) run on the device, fused with the normalisation in front of the stem (a3d_preprocess_resize_u8).
 Output: <output>/predictions.json -- per frame the optimised detections (bbox xyxy, score, class, plane, rotation /
 translation axis, RLE mask) and <output>/tracks.json (tracked planes, has_rot, consensus axis).
-`--vis png|npy` also writes the reference's 2-D visualisation, the four panels per frame of its output.mp4
+`--vis png|npy|avi` also writes the reference's 2-D visualisation, the four panels per frame of its output.mp4
 (`[opt seg | opt normal | raw seg | raw normal]`, [480, 2560, 3] uint8 RGB), rendered on the GPU (articulation3d_amd/render.py):
-<output>/vis/frame_%05d.png or one <output>/vis.npy.  There is no video encoder here, so no .mp4.
+<output>/vis/frame_%05d.png, one <output>/vis.npy, or the video <output>/output.avi.  The video is Motion-JPEG in an AVI container,
+not the reference's H.264 .mp4: every frame is a baseline JPEG (4:4:4, `--vis-quality`), encoded on the GPU
+(articulation3d_amd/video.py), played at `--fps` (a .npy or an image directory carries no frame rate; the reference takes its reader's).
 `--save-obj` writes the reference's 3-D model (its save_obj_model, :44-168) for the frames of `--obj-frames`:
 <output>/frame_%04d/arti_pred.obj + .mtl + uv_maps/*.png -- the most confident articulated plane in its opened poses, two axis
 markers and the background, as dense meshes built on the GPU (articulation3d_amd/mesh.py states the departures).
@@ -110,7 +112,8 @@ def write_visualisation(args, device, frames_rgb, raw_preds, opt_preds, chunk: i
     """--vis: resize the clip's frames on the device in chunks of `chunk` source frames (the detector's own front end, uint8
     output, 0.9 MB per resized frame kept on the device), then ONE render_clip over the whole clip: its buffers are pinned and
     allocated once, and the four-panel rows are written as they come off the copy pipeline.  render_clip works in chunks of 8
-    frames: 3.7 MB per row, so 88 MB of pinned memory in its three host buffers."""
+    frames: 3.7 MB per row, so 88 MB of pinned memory in its three host buffers.  `--vis avi` goes through render_clip_jpeg instead:
+    the rows are encoded on the device and only the JPEG bytes come to the host, straight into <output>/output.avi."""
     from articulation3d_amd import ops
     from articulation3d_amd.render import render_clip
 
@@ -123,8 +126,17 @@ def write_visualisation(args, device, frames_rgb, raw_preds, opt_preds, chunk: i
         from PIL import Image
 
         os.makedirs(os.path.join(args.output, "vis"), exist_ok=True)
-    else:
+    elif args.vis == "npy":
         whole = np.lib.format.open_memmap(os.path.join(args.output, "vis.npy"), mode="w+", dtype=np.uint8, shape=(n, 480, 4 * 640, 3))
+    if args.vis == "avi":
+        from articulation3d_amd.video import MJPEGWriter, render_clip_jpeg
+
+        with MJPEGWriter(os.path.join(args.output, "output.avi"), 4 * 640, 480, args.fps) as video:
+            for jpegs in render_clip_jpeg(u8, raw_preds, opt_preds, quality=args.vis_quality, chunk=8, mask_alpha=args.mask_alpha,
+                                          conf_threshold=args.conf_threshold):
+                for jpeg in jpegs:
+                    video.write(jpeg)
+        return
     at = 0
     for rows in render_clip(u8, raw_preds, opt_preds, chunk=8, mask_alpha=args.mask_alpha, conf_threshold=args.conf_threshold):
         if args.vis == "png":
@@ -179,10 +191,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--no-precision-audit", action="store_true",
                     help="skip the load-time audit of the default arithmetic (PlaneRCNN.audit_precision: every fp16x2 layer checked against its "
                          "bf16x3 evaluation on the clip's first frames; layers that leave the format's window are pinned to bf16x3)")
-    ap.add_argument("--vis", choices=("none", "png", "npy"), default="none",
+    ap.add_argument("--vis", choices=("none", "png", "npy", "avi"), default="none",
                     help="write the reference's four-panel visualisation row per frame (opt seg | opt normal | raw seg | raw normal), rendered on "
-                         "the GPU: png = <output>/vis/frame_%%05d.png, npy = one <output>/vis.npy [F,480,2560,3].  .mp4 is unavailable: there is "
-                         "no video encoder in this environment")
+                         "the GPU: png = <output>/vis/frame_%%05d.png, npy = one <output>/vis.npy [F,480,2560,3], avi = the video "
+                         "<output>/output.avi, Motion-JPEG (baseline JPEG frames encoded on the GPU) in an AVI container -- not the reference's "
+                         "H.264 .mp4, which needs an encoder this package does not have")
+    ap.add_argument("--vis-quality", default=90, type=int, help="--vis avi: JPEG quality, 1 .. 100")
+    ap.add_argument("--fps", default="30", help="--vis avi: frames per second, an integer or a ratio such as 30000/1001")
     ap.add_argument("--mask-alpha", default=0.0, type=float,
                     help="--vis: opacity of the instance masks on the seg panels (0 = none, as the reference draws them)")
     ap.add_argument("--save-obj", action="store_true",
