@@ -391,7 +391,7 @@ __global__ __launch_bounds__(256) void plane_offset_dense_kernel(const float *__
 
 extern "C" int a3d_plane_offset_dense(const float *depth, const float *masks, const float *normals, float *out, int D,
                                       int H, int W, float focal, float cx, float cy, void *stream) {
-    if (!depth || !masks || !normals || !out || D < 0 || H > 2048 || W > 2048) return A3D_ERR_ARG;
+    if (!depth || !masks || !normals || !out || D < 0 || H <= 0 || W <= 0 || H > 2048 || W > 2048) return A3D_ERR_ARG;  // (the kernel divides by W)
     if (D == 0) return A3D_OK;
     a3d_begin();
     hipLaunchKernelGGL(plane_offset_dense_kernel<float>, dim3(D), dim3(256), 0, (hipStream_t)stream, depth, masks, normals, out,
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(1024) void plane_offset_dense_u8_kernel(const float
 
 extern "C" int a3d_plane_offset_dense_u8(const float *depth, const unsigned char *masks, const float *normals, float *out, int D,
                                          int H, int W, float focal, float cx, float cy, void *stream) {
-    if (!depth || !masks || !normals || !out || D < 0 || H > 2048 || W > 2048) return A3D_ERR_ARG;
+    if (!depth || !masks || !normals || !out || D < 0 || H <= 0 || W <= 0 || H > 2048 || W > 2048) return A3D_ERR_ARG;
     if (D == 0) return A3D_OK;
     a3d_begin();
     hipLaunchKernelGGL(plane_offset_dense_u8_kernel, dim3(D), dim3(1024), 0, (hipStream_t)stream, depth, masks, normals, out, H, W, focal, cx, cy);

@@ -51,8 +51,8 @@ __global__ __launch_bounds__(256) void pack_kernel(const PackArgs a) {
             else v = a.tran_axis ? a.tran_axis[(size_t)row * 2 + (t - 12)] : 0.f;
             o[t] = v;
         }
-        if (a.mask_prob)
-            for (int i = threadIdx.x; i < mm; i += blockDim.x) o[REC_HEAD + i] = a.mask_prob[(size_t)row * mm + i];
+        // (no mask: zeros, like the other optional fields -- the record buffer is not cleared by the caller)
+        for (int i = threadIdx.x; i < mm; i += blockDim.x) o[REC_HEAD + i] = a.mask_prob ? a.mask_prob[(size_t)row * mm + i] : 0.f;
     }
     // zero the unused tail so the gathered buffer is deterministic
     for (size_t i = (size_t)total * rec + threadIdx.x; i < (size_t)a.R * rec; i += blockDim.x) out[i] = 0.f;
