@@ -5,7 +5,7 @@
 // The rows are the compacted foreground ROIs [0, *live) of a batch; the loss is a mean over the valid rows of the WHOLE batch, so
 // the launch is one workgroup: pass 1 sums counts and losses (per thread in row order, then a fixed tree), pass 2 writes the gradients
 // of (loss_rot + loss_tran) with respect to the raw head outputs.  No atomics: the same bits on every run.
-#include "a3d_common.h"
+#include "kernel_prims.h"
 #include "../../include/a3d.h"
 
 namespace {
@@ -64,26 +64,12 @@ __device__ __forceinline__ AxRow ax_row(const a3d_axis_loss_desc &d, int r) {
     return q;
 }
 
-// d(v / max(|v|, eps)) backward: gradient with respect to v = (a, b) given the gradient (gs, gc) of the normalised pair
-__device__ __forceinline__ void ax_norm_bwd(float a, float b, float n, float dn, float gs, float gc, float &ga, float &gb) {
-    ga = gs / dn;
-    gb = gc / dn;
-    if (n >= AX_EPS) {  // (clamp_min passes the gradient where |v| >= eps; there dn == n > 0)
-        const float dd = -(gs * a + gc * b) / (dn * dn);
-        ga += dd * a / n;
-        gb += dd * b / n;
-    }
-}
-
+// the block's sum of v in every thread; `red` is free again on return
 template <typename T>
-__device__ __forceinline__ T ax_reduce(T v, T *red) {  // fixed pairing: bit-reproducible
-    const int t = threadIdx.x;
-    red[t] = v;
+__device__ __forceinline__ T ax_reduce(T v, T *red) {
+    red[threadIdx.x] = v;
     __syncthreads();
-    for (int w = AX_THREADS / 2; w > 0; w >>= 1) {
-        if (t < w) red[t] = red[t] + red[t + w];
-        __syncthreads();
-    }
+    a3d_lds_tree<AX_THREADS>(red);
     const T s = red[0];
     __syncthreads();
     return s;
@@ -92,8 +78,7 @@ __device__ __forceinline__ T ax_reduce(T v, T *red) {  // fixed pairing: bit-rep
 __global__ __launch_bounds__(AX_THREADS) void axis_loss_kernel(const a3d_axis_loss_desc d) {
     __shared__ float redf[AX_THREADS];
     __shared__ int redi[AX_THREADS];
-    const int nl = __builtin_amdgcn_readfirstlane(*d.live);
-    const int live = nl < 0 ? 0 : (nl < d.rows ? nl : d.rows);
+    const int live = a3d_live_rows(d.live, d.rows);
     // ---- pass 1: valid counts, valid-column sums and loss sums of both axes
     float vsr = 0.f, vst = 0.f, lr = 0.f, lt = 0.f;
     int cr = 0, ct = 0;
@@ -131,15 +116,15 @@ __global__ __launch_bounds__(AX_THREADS) void axis_loss_kernel(const a3d_axis_lo
         if (r < live) {
             const AxRow q = ax_row(d, r);
             if (q.ok && onr && q.vr >= 0.5f) {
-                const float gs = kr * ax_sl1_grad(q.e[0], d.beta), gc = kr * ax_sl1_grad(q.e[1], d.beta);
-                ax_norm_bwd(q.a, q.b, q.n, q.dn, gs, gc, gr[0], gr[1]);
+                const float gn[2] = {kr * ax_sl1_grad(q.e[0], d.beta), kr * ax_sl1_grad(q.e[1], d.beta)}, v[2] = {q.a, q.b};
+                a3d_norm_bwd<2>(v, q.n, q.dn, AX_EPS, gn, gr);
                 gr[2] = kr * ax_sl1_grad(q.e[2], d.beta);
             }
             if (q.ok && ont && q.vt >= 0.5f) {
                 const float g0 = kt * ax_sl1_grad(q.f[0], d.beta), g1 = kt * ax_sl1_grad(q.f[1], d.beta);
                 // double_angle backward: d(2sc)/ds = 2c, d(2sc)/dc = 2s, d(c^2 - s^2)/ds = -2s, d(c^2 - s^2)/dc = 2c
-                const float gs = g0 * (2.f * q.tc) - g1 * (2.f * q.ts), gc = g0 * (2.f * q.ts) + g1 * (2.f * q.tc);
-                ax_norm_bwd(q.ta, q.tb, q.tn, q.tdn, gs, gc, gt[0], gt[1]);
+                const float gn[2] = {g0 * (2.f * q.tc) - g1 * (2.f * q.ts), g0 * (2.f * q.ts) + g1 * (2.f * q.tc)}, v[2] = {q.ta, q.tb};
+                a3d_norm_bwd<2>(v, q.tn, q.tdn, AX_EPS, gn, gt);
             }
         }
         float *dr = d.d_rot + (size_t)r * d.rot_pitch;

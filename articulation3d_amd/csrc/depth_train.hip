@@ -9,7 +9,7 @@
 // and keeps its four channels' sums in registers.  No atomics anywhere: every sum leaves its workgroup as a partial and a later launch
 // folds the partials in index order, so every call gives the same bits.  Built with -ffp-contract=off: the bilinear weights and the L1
 // tail round like the reference's separate operators.
-#include "a3d_common.h"
+#include "kernel_prims.h"
 #include "../../include/a3d.h"
 
 namespace {
@@ -27,16 +27,13 @@ __host__ __device__ inline int dt_rows_per_part(int N) {
     return r < DT_MIN_ROWS ? DT_MIN_ROWS : r;
 }
 
-__device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
-__device__ __forceinline__ void st4(float *p, const f32x4 v) { *reinterpret_cast<f32x4 *>(p) = v; }
-
 // Sum over the strands of a workgroup: strand s holds acc for channels sub * 4 .. + 3 -> red[s][C]; threads t < C then add the strands
 // in order.  (red is reused by the caller: barriers on both sides)
 template <int C>
 __device__ __forceinline__ float dt_fold_strands(float (*red)[C], const f32x4 acc, int s, int sub) {
     constexpr int S = DT_THREADS / (C / 4);
     __syncthreads();
-    st4(&red[s][sub * 4], acc);
+    a3d_st4(&red[s][sub * 4], acc);
     __syncthreads();
     float a = 0.f;
     if ((int)threadIdx.x < C) {
@@ -58,23 +55,23 @@ __global__ __launch_bounds__(DT_THREADS) void bn_stats_kernel(const a3d_bn_train
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     int r = r0 + s;
     for (; r + 3 * S < r1; r += 4 * S) {  // four independent 16-byte loads in flight per lane
-        const f32x4 a = ld4(z + (size_t)r * C), b = ld4(z + (size_t)(r + S) * C), c = ld4(z + (size_t)(r + 2 * S) * C), e = ld4(z + (size_t)(r + 3 * S) * C);
+        const f32x4 a = a3d_ld4(z + (size_t)r * C), b = a3d_ld4(z + (size_t)(r + S) * C), c = a3d_ld4(z + (size_t)(r + 2 * S) * C), e = a3d_ld4(z + (size_t)(r + 3 * S) * C);
         acc += (a + b) + (c + e);
     }
-    for (; r < r1; r += S) acc += ld4(z + (size_t)r * C);
+    for (; r < r1; r += S) acc += a3d_ld4(z + (size_t)r * C);
     const float sum = dt_fold_strands<C>(red, acc, s, sub);
     if ((int)threadIdx.x < C) mu[threadIdx.x] = sum / (float)n;
     __syncthreads();
-    const f32x4 m = ld4(&mu[sub * 4]);
+    const f32x4 m = a3d_ld4(&mu[sub * 4]);
     acc = f32x4{0.f, 0.f, 0.f, 0.f};
     r = r0 + s;
     for (; r + 3 * S < r1; r += 4 * S) {  // (the workgroup's own rows again: served from L2)
-        const f32x4 a = ld4(z + (size_t)r * C) - m, b = ld4(z + (size_t)(r + S) * C) - m, c = ld4(z + (size_t)(r + 2 * S) * C) - m,
-                    e = ld4(z + (size_t)(r + 3 * S) * C) - m;
+        const f32x4 a = a3d_ld4(z + (size_t)r * C) - m, b = a3d_ld4(z + (size_t)(r + S) * C) - m, c = a3d_ld4(z + (size_t)(r + 2 * S) * C) - m,
+                    e = a3d_ld4(z + (size_t)(r + 3 * S) * C) - m;
         acc += (a * a + b * b) + (c * c + e * e);
     }
     for (; r < r1; r += S) {
-        const f32x4 a = ld4(z + (size_t)r * C) - m;
+        const f32x4 a = a3d_ld4(z + (size_t)r * C) - m;
         acc += a * a;
     }
     const float m2 = dt_fold_strands<C>(red, acc, s, sub);
@@ -138,15 +135,15 @@ template <int C>
 __global__ __launch_bounds__(DT_THREADS) void bn_apply_kernel(const a3d_bn_train_desc d) {
     constexpr int LPR = C / 4;
     const int sub = threadIdx.x % LPR;  // (the grid stride is a multiple of LPR: a thread keeps its channels)
-    const f32x4 m = ld4(d.mean + sub * 4), is = ld4(d.invstd + sub * 4), ga = ld4(d.gamma + sub * 4), be = ld4(d.beta + sub * 4);
+    const f32x4 m = a3d_ld4(d.mean + sub * 4), is = a3d_ld4(d.invstd + sub * 4), ga = a3d_ld4(d.gamma + sub * 4), be = a3d_ld4(d.beta + sub * 4);
     const f32x4 sc = ga * is;
     const size_t total = (size_t)d.N * LPR;
     for (size_t i = (size_t)blockIdx.x * DT_THREADS + threadIdx.x; i < total; i += (size_t)gridDim.x * DT_THREADS) {
-        const f32x4 v = (ld4(d.z + i * 4) - m) * sc + be;
+        const f32x4 v = (a3d_ld4(d.z + i * 4) - m) * sc + be;
         f32x4 o;
 #pragma unroll
         for (int k = 0; k < 4; ++k) o[k] = dt_act(v[k], d.act);
-        st4(d.y + i * 4, o);
+        a3d_st4(d.y + i * 4, o);
     }
 }
 
@@ -157,12 +154,12 @@ __global__ __launch_bounds__(DT_THREADS) void bn_bwd_reduce_kernel(const a3d_bn_
     __shared__ __attribute__((aligned(16))) float red[S][C];
     const int sub = threadIdx.x % LPR, s = threadIdx.x / LPR;
     const int r0 = blockIdx.x * R, r1 = min(d.N, r0 + R);
-    const f32x4 m = ld4(d.mean + sub * 4), is = ld4(d.invstd + sub * 4);
+    const f32x4 m = a3d_ld4(d.mean + sub * 4), is = a3d_ld4(d.invstd + sub * 4);
     f32x4 sg = {0.f, 0.f, 0.f, 0.f}, sx = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 2
     for (int r = r0 + s; r < r1; r += S) {
         const size_t at = (size_t)r * C + sub * 4;
-        const f32x4 dy = ld4(d.dy + (size_t)r * d.dy_pitch + d.dy_off + sub * 4), y = ld4(d.y + at), z = ld4(d.z + at);
+        const f32x4 dy = a3d_ld4(d.dy + (size_t)r * d.dy_pitch + d.dy_off + sub * 4), y = a3d_ld4(d.y + at), z = a3d_ld4(d.z + at);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float g = dy[k] * dt_act_grad(y[k], d.act);
@@ -199,26 +196,21 @@ template <int C>
 __global__ __launch_bounds__(DT_THREADS) void bn_bwd_apply_kernel(const a3d_bn_train_desc d) {
     constexpr int LPR = C / 4;
     const int sub = threadIdx.x % LPR;
-    const f32x4 m = ld4(d.mean + sub * 4), is = ld4(d.invstd + sub * 4), ga = ld4(d.gamma + sub * 4);
+    const f32x4 m = a3d_ld4(d.mean + sub * 4), is = a3d_ld4(d.invstd + sub * 4), ga = a3d_ld4(d.gamma + sub * 4);
     const float inv_n = 1.f / (float)d.N;
-    const f32x4 mg = ld4(d.dbeta + sub * 4) * inv_n, mx = ld4(d.dgamma + sub * 4) * inv_n, sc = ga * is;
+    const f32x4 mg = a3d_ld4(d.dbeta + sub * 4) * inv_n, mx = a3d_ld4(d.dgamma + sub * 4) * inv_n, sc = ga * is;
     const size_t total = (size_t)d.N * LPR;
     for (size_t i = (size_t)blockIdx.x * DT_THREADS + threadIdx.x; i < total; i += (size_t)gridDim.x * DT_THREADS) {
         const size_t r = i / LPR;
-        const f32x4 dy = ld4(d.dy + r * d.dy_pitch + d.dy_off + sub * 4), y = ld4(d.y + i * 4), z = ld4(d.z + i * 4);
+        const f32x4 dy = a3d_ld4(d.dy + r * d.dy_pitch + d.dy_off + sub * 4), y = a3d_ld4(d.y + i * 4), z = a3d_ld4(d.z + i * 4);
         f32x4 o;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float g = dy[k] * dt_act_grad(y[k], d.act);
             o[k] = sc[k] * ((g - mg[k]) - ((z[k] - m[k]) * is[k]) * mx[k]);
         }
-        st4(d.dz + i * 4, o);
+        a3d_st4(d.dz + i * 4, o);
     }
-}
-
-inline int dt_stream_grid(size_t total) {  // an HBM-bound element pass: at most 2048 workgroups, grid-stride beyond
-    const size_t b = (total + DT_THREADS - 1) / DT_THREADS;
-    return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
 
 int bn_check(const a3d_bn_train_desc *d, bool backward) {
@@ -237,16 +229,6 @@ int bn_check(const a3d_bn_train_desc *d, bool backward) {
 }
 
 // ---- the loss ---------------------------------------------------------------------------------------------------------------------------
-// aten upsample_bilinear2d's source index, align_corners false: spatial_ops.hip's src_index
-__device__ __forceinline__ void dl_src_index(int o, float scale, int in_size, int &i0, int &i1, float &l1) {
-    float s = scale * ((float)o + 0.5f) - 0.5f;
-    if (s < 0.f) s = 0.f;
-    i0 = (int)s;
-    if (i0 > in_size - 1) i0 = in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = s - (float)i0;
-}
-
 // One thread per low-resolution pixel (grid-stride): it visits the up to 4 x 4 output pixels whose bilinear footprint holds it, forms
 // each one's prediction with the resize kernel's arithmetic and collects sign(pred - gt) x its own weight there; the 2 x 2 outputs it
 // owns (oy >> 1 == y, ox >> 1 == x) also go into its loss sum and its count, so every output pixel is counted once.
@@ -265,7 +247,7 @@ __global__ __launch_bounds__(DT_THREADS) void depth_loss_gather_kernel(const a3d
         for (int oy = max(2 * y - 1, 0); oy <= min(2 * y + 2, H - 1); ++oy) {
             int y0, y1;
             float ly;
-            dl_src_index(oy, 0.5f, h, y0, y1, ly);
+            a3d_src_index(oy, 0.5f, h, y0, y1, ly);
             const float hy = 1.f - ly;
             const float wy = (y0 == y ? hy : 0.f) + (y1 == y ? ly : 0.f);
             for (int ox = max(2 * x - 1, 0); ox <= min(2 * x + 2, W - 1); ++ox) {
@@ -273,7 +255,7 @@ __global__ __launch_bounds__(DT_THREADS) void depth_loss_gather_kernel(const a3d
                 if (!(t > DT_VALID)) continue;
                 int x0, x1;
                 float lx;
-                dl_src_index(ox, 0.5f, w, x0, x1, lx);
+                a3d_src_index(ox, 0.5f, w, x0, x1, lx);
                 const float hx = 1.f - lx;
                 const float wx = (x0 == x ? hx : 0.f) + (x1 == x ? lx : 0.f);
                 const float p = hy * (hx * src[(size_t)y0 * w + x0] + lx * src[(size_t)y0 * w + x1]) +
@@ -291,13 +273,7 @@ __global__ __launch_bounds__(DT_THREADS) void depth_loss_gather_kernel(const a3d
     red[threadIdx.x] = ls;
     redn[threadIdx.x] = cnt;
     __syncthreads();
-    for (int s = DT_THREADS / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            red[threadIdx.x] += red[threadIdx.x + s];
-            redn[threadIdx.x] += redn[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    a3d_lds_tree<DT_THREADS>(red, redn);
     if (threadIdx.x == 0) {
         d.workspace[2 * blockIdx.x] = red[0];
         reinterpret_cast<int *>(d.workspace)[2 * blockIdx.x + 1] = redn[0];
@@ -313,13 +289,7 @@ __global__ __launch_bounds__(DT_THREADS) void depth_loss_scale_kernel(const a3d_
     red[t] = t < parts ? (double)d.workspace[2 * t] : 0.0;  // (parts <= DT_THREADS)
     redn[t] = t < parts ? (long long)reinterpret_cast<const int *>(d.workspace)[2 * t + 1] : 0;
     __syncthreads();
-    for (int s = DT_THREADS / 2; s > 0; s >>= 1) {
-        if (t < s) {
-            red[t] += red[t + s];
-            redn[t] += redn[t + s];
-        }
-        __syncthreads();
-    }
+    a3d_lds_tree<DT_THREADS>(red, redn);
     const long long n = redn[0] > 0 ? redn[0] : 1;
     if (blockIdx.x == 0 && t == 0) {
         d.out[0] = (float)((double)d.loss_weight * red[0] / (double)n);
@@ -342,14 +312,14 @@ __global__ __launch_bounds__(DT_THREADS) void pred_bwd_kernel(const a3d_pred_bwd
     f32x4 wt[9], dw[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-        wt[t] = ld4(d.w + t * C + sub * 4);
+        wt[t] = a3d_ld4(d.w + t * C + sub * 4);
         dw[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     float db = 0.f;
     for (size_t q = (size_t)blockIdx.x * S + s; q < total; q += (size_t)gridDim.x * S) {
         const int x = (int)(q % W), y = (int)((q / W) % H);
         const float *gb = d.g + (q - (size_t)y * W - x);  // the image's gradient map
-        const f32x4 v = ld4(d.x + q * C + sub * 4);
+        const f32x4 v = a3d_ld4(d.x + q * C + sub * 4);
         f32x4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
@@ -361,7 +331,7 @@ __global__ __launch_bounds__(DT_THREADS) void pred_bwd_kernel(const a3d_pred_bwd
                 dw[ky * 3 + kx] += v * g;
             }
         }
-        st4(d.dx + q * C + sub * 4, o);
+        a3d_st4(d.dx + q * C + sub * 4, o);
         db += gb[(size_t)y * W + x];
     }
     float *part = d.workspace + (size_t)blockIdx.x * (9 * C + 4);
@@ -408,7 +378,7 @@ __global__ __launch_bounds__(DT_THREADS) void ups2_concat_kernel(const float *__
         const int oy = (int)(p % Ho);
         const size_t b = p / Ho;
         const size_t src = (b * H + (oy >> 1)) * W + (ox >> 1);
-        st4(out + i * 4, c < Ca ? ld4(a + src * Ca + c) : ld4(b2 + src * Cb + (c - Ca)));
+        a3d_st4(out + i * 4, c < Ca ? a3d_ld4(a + src * Ca + c) : a3d_ld4(b2 + src * Cb + (c - Ca)));
     }
 }
 
@@ -428,19 +398,19 @@ __global__ __launch_bounds__(DT_THREADS) void resize_bilinear_bwd_kernel(const f
         for (int oy = 0; oy < Ho; ++oy) {
             int y0, y1;
             float ly;
-            dl_src_index(oy, sh, H, y0, y1, ly);
+            a3d_src_index(oy, sh, H, y0, y1, ly);
             const float wy = (y0 == iy ? 1.f - ly : 0.f) + (y1 == iy ? ly : 0.f);
             if (y0 != iy && y1 != iy) continue;
             for (int ox = 0; ox < Wo; ++ox) {
                 int x0, x1;
                 float lx;
-                dl_src_index(ox, sw, W, x0, x1, lx);
+                a3d_src_index(ox, sw, W, x0, x1, lx);
                 if (x0 != ix && x1 != ix) continue;
                 const float wx = (x0 == ix ? 1.f - lx : 0.f) + (x1 == ix ? lx : 0.f);
-                acc += ld4(dy + ((b * Ho + oy) * Wo + ox) * C + c) * (wy * wx);
+                acc += a3d_ld4(dy + ((b * Ho + oy) * Wo + ox) * C + c) * (wy * wx);
             }
         }
-        st4(dx + i * 4, acc);
+        a3d_st4(dx + i * 4, acc);
     }
 }
 }  // namespace
@@ -455,7 +425,7 @@ extern "C" int a3d_bn_train_forward(const a3d_bn_train_desc *d, void *stream) {
     if (rc != A3D_OK) return rc;
     const hipStream_t s = (hipStream_t)stream;
     const int R = dt_rows_per_part(d->N), parts = (d->N + R - 1) / R;
-    const int grid = dt_stream_grid((size_t)d->N * (d->C / 4));
+    const int grid = a3d_stream_grid((size_t)d->N * (d->C / 4));
     a3d_begin();
     if (d->C == 64) {
         hipLaunchKernelGGL(bn_stats_kernel<64>, dim3(parts), dim3(DT_THREADS), 0, s, *d, R);
@@ -474,7 +444,7 @@ extern "C" int a3d_bn_train_backward(const a3d_bn_train_desc *d, void *stream) {
     if (rc != A3D_OK) return rc;
     const hipStream_t s = (hipStream_t)stream;
     const int R = dt_rows_per_part(d->N), parts = (d->N + R - 1) / R;
-    const int grid = dt_stream_grid((size_t)d->N * (d->C / 4));
+    const int grid = a3d_stream_grid((size_t)d->N * (d->C / 4));
     a3d_begin();
     if (d->C == 64) {
         hipLaunchKernelGGL(bn_bwd_reduce_kernel<64>, dim3(parts), dim3(DT_THREADS), 0, s, *d, R);
@@ -521,7 +491,7 @@ extern "C" int a3d_ups2_concat(const float *a, const float *b2, float *out, int 
     if (!a || !out || B <= 0 || H <= 0 || W <= 0 || Ca <= 0 || Cb < 0 || (Ca & 3) || (Cb & 3) || (Cb > 0 && !b2)) return A3D_ERR_ARG;
     if (((uintptr_t)a | (uintptr_t)b2 | (uintptr_t)out) & 15) return A3D_ERR_ARG;
     a3d_begin();
-    hipLaunchKernelGGL(ups2_concat_kernel, dim3(dt_stream_grid((size_t)B * 4 * H * W * ((Ca + Cb) / 4))), dim3(DT_THREADS), 0, (hipStream_t)stream, a, b2,
+    hipLaunchKernelGGL(ups2_concat_kernel, dim3(a3d_stream_grid((size_t)B * 4 * H * W * ((Ca + Cb) / 4))), dim3(DT_THREADS), 0, (hipStream_t)stream, a, b2,
                        out, B, H, W, Ca, Cb);
     return a3d_check_launch();
 }
@@ -531,7 +501,7 @@ extern "C" int a3d_resize_bilinear_backward_nhwc(const float *dy, float *dx, int
     if (((uintptr_t)dy | (uintptr_t)dx) & 15) return A3D_ERR_ARG;
     const float sh = (float)H / (float)Ho, sw = (float)W / (float)Wo;
     a3d_begin();
-    hipLaunchKernelGGL(resize_bilinear_bwd_kernel, dim3(dt_stream_grid((size_t)B * H * W * (C / 4))), dim3(DT_THREADS), 0, (hipStream_t)stream, dy, dx, B, H,
+    hipLaunchKernelGGL(resize_bilinear_bwd_kernel, dim3(a3d_stream_grid((size_t)B * H * W * (C / 4))), dim3(DT_THREADS), 0, (hipStream_t)stream, dy, dx, B, H,
                        W, C, Ho, Wo, sh, sw);
     return a3d_check_launch();
 }

@@ -10,6 +10,7 @@
 // workgroup per (class, metric), one workgroup per depth map.  No atomics on floats and no reduction whose order depends on timing:
 // the only atomic is an integer minimum in LDS, so every call gives the same bits.  Built with -ffp-contract=off: every operator
 // rounds on its own, as numpy's do.
+#include "kernel_prims.h"
 #include "eval_common.h"  // the box IoU, a detection's ground truth and rank: shared with csrc/plane_eval.hip
 
 #include <limits.h>
@@ -180,7 +181,7 @@ __global__ __launch_bounds__(AP_THREADS) void eval_ap_kernel(const ApArgs a) {
     // the segment's number of true positives
     int cnt = 0;
     for (int i = tid; i < n; i += AP_THREADS) cnt += (tp[i] >> m) & 1;
-    for (int off = 1; off < A3D_WAVE; off <<= 1) cnt += __shfl_xor(cnt, off, A3D_WAVE);
+    cnt = a3d_wave_sum(cnt);
     if (lane == 0) wsum[wv] = cnt;
     __syncthreads();
     int end_cum = 0;
@@ -191,19 +192,9 @@ __global__ __launch_bounds__(AP_THREADS) void eval_ap_kernel(const ApArgs a) {
     for (int i0 = ((n - 1) / AP_THREADS) * AP_THREADS; i0 >= 0; i0 -= AP_THREADS) {
         const int i = i0 + tid;
         const int bit = i < n ? (tp[i] >> m) & 1 : 0;
-        int incl = bit;
-        for (int off = 1; off < A3D_WAVE; off <<= 1) {
-            const int u = __shfl_up(incl, off, A3D_WAVE);
-            if (lane >= off) incl += u;
-        }
-        if (lane == A3D_WAVE - 1) wsum[wv] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < NW; ++w) {
-            before += w < wv ? wsum[w] : 0;
-            total += wsum[w];
-        }
-        const int cum = end_cum - total + before + incl;  // true positives among entries 0 .. i
+        int total;
+        const int before = a3d_block_exclusive_scan<AP_THREADS>(bit, wsum, total);
+        const int cum = end_cum - total + before + bit;  // true positives among entries 0 .. i
         const double prec = i < n ? (double)cum / (double)(i + 1) : 0.0;
         double mx = prec;  // suffix maximum within the wave, then over the later waves and the later passes
         for (int off = 1; off < A3D_WAVE; off <<= 1) {
@@ -224,10 +215,7 @@ __global__ __launch_bounds__(AP_THREADS) void eval_ap_kernel(const ApArgs a) {
     }
     part[tid] = acc;
     __syncthreads();
-    for (int s = AP_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) part[tid] += part[tid + s];
-        __syncthreads();
-    }
+    a3d_lds_tree<AP_THREADS>(part);
     if (tid == 0) a.ap[(size_t)m * a.C + c] = part[0];
 }
 
@@ -249,13 +237,7 @@ __global__ __launch_bounds__(DL1_THREADS) void depth_l1_kernel(const a3d_depth_l
     ssum[threadIdx.x] = s;
     scnt[threadIdx.x] = n;
     __syncthreads();
-    for (int k = DL1_THREADS / 2; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) {
-            ssum[threadIdx.x] += ssum[threadIdx.x + k];
-            scnt[threadIdx.x] += scnt[threadIdx.x + k];
-        }
-        __syncthreads();
-    }
+    a3d_lds_tree<DL1_THREADS>(ssum, scnt);
     if (threadIdx.x == 0) {
         d.sum[blockIdx.x] = ssum[0];
         d.count[blockIdx.x] = scnt[0];

@@ -5,7 +5,7 @@
 //                  (mask_ops.py:41-60,128-129) and the per-ROI plane-offset least squares
 //                  (arti_vis.py:90-99,125-149) fused: the pasted mask is consumed in registers.
 // Built with -ffp-contract=off so the paste coordinates round like the reference's separate ops.
-#include "a3d_common.h"
+#include "kernel_prims.h"
 #include "../../include/a3d.h"
 
 #define SMALL_N_MAX 8
@@ -43,7 +43,7 @@ __device__ __forceinline__ void linear_small_rows(const float *__restrict__ x, c
         if (r >= nrows) break;
 #pragma unroll
         for (int n = 0; n < SMALL_N_MAX; ++n)
-            for (int off = 32; off > 0; off >>= 1) acc[r][n] += __shfl_xor(acc[r][n], off, 64);
+            acc[r][n] = a3d_wave_sum(acc[r][n]);
         if (lane == 0) {
             float v[SMALL_N_MAX];
             for (int n = 0; n < N; ++n) v[n] = acc[r][n] + (bias ? bias[n] : 0.f);
@@ -245,10 +245,11 @@ __global__ __launch_bounds__(PASTE_THREADS) void paste_lsq_kernel(const PasteArg
             *reinterpret_cast<uint4 *>(mout + (size_t)py * a.W + gx) = pk;
         }
     }
-    // workgroup reduction (fixed order: lanes by xor-shuffle, then the waves in order)
-    for (int off = 32; off > 0; off >>= 1) {
-        sum += __shfl_xor(sum, off, 64);
-        cntpix += __shfl_xor(cntpix, off, 64);
+    // workgroup reduction (fixed order: lanes by xor-shuffle, then the waves in order).  a3d_wave_sum's butterfly written out: through
+    // the helper the paste loop above picks other multiplies and four more registers.
+    for (int off = A3D_WAVE / 2; off > 0; off >>= 1) {
+        sum += __shfl_xor(sum, off, A3D_WAVE);
+        cntpix += __shfl_xor(cntpix, off, A3D_WAVE);
     }
     const int wave = threadIdx.x >> 6;
     __shared__ double sred[PASTE_WAVES];
@@ -364,9 +365,10 @@ __global__ __launch_bounds__(256) void plane_offset_dense_kernel(const float *__
             ++py;
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        sum += __shfl_xor(sum, off, 64);
-        c += __shfl_xor(c, off, 64);
+    // (a3d_wave_sum's butterfly written out: through the helper the float form's loop above pairs its multiplies differently)
+    for (int off = A3D_WAVE / 2; off > 0; off >>= 1) {
+        sum += __shfl_xor(sum, off, A3D_WAVE);
+        c += __shfl_xor(c, off, A3D_WAVE);
     }
     if ((threadIdx.x & 63) == 0) {
         sred[threadIdx.x >> 6] = sum;
@@ -445,10 +447,8 @@ __global__ __launch_bounds__(1024) void plane_offset_dense_u8_kernel(const float
             }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        sum += __shfl_xor(sum, off, 64);
-        c += __shfl_xor(c, off, 64);
-    }
+    sum = a3d_wave_sum(sum);
+    c = a3d_wave_sum(c);
     if ((threadIdx.x & 63) == 0) {
         sred[threadIdx.x >> 6] = sum;
         redc[threadIdx.x >> 6] = c;

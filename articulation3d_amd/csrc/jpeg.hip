@@ -21,7 +21,7 @@
 // of them); the transform clamps to those ranges all the same, so the bound holds whatever the arithmetic above it does.  A tile
 // of 256 blocks is therefore at most 7 carried bits + 256 * 1658 bits = 13265 words of LDS, and a segment of M MCUs at most
 // ceil(3 M * 1658 / 8) bytes before and twice that after stuffing (the filled last byte included): a3d_jpeg_slot_bytes.
-#include "a3d_common.h"
+#include "kernel_prims.h"
 #include "../../include/a3d.h"
 
 namespace {
@@ -189,23 +189,12 @@ __global__ __launch_bounds__(256) void jpeg_transform_kernel(const unsigned char
     for (int i = tid; i < n16; i += 256) dst[i] = reinterpret_cast<const uint4 *>(sQ)[i];
 }
 
-// exclusive scan of one int per lane over the 256-lane workgroup; `total` is the same in every lane.  s: 4 words of LDS.
+// exclusive scan of one int per lane over the 256-lane workgroup; `total` is the same in every lane.  s: 4 words of LDS, free again
+// on return.
 __device__ __forceinline__ int scan256(const int v, int *s, int &total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) s[wv] = x;
+    const int excl = a3d_block_exclusive_scan<256>(v, s, total);
     __syncthreads();
-    int base = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) base += i < wv ? s[i] : 0;
-    total = s[0] + s[1] + s[2] + s[3];
-    __syncthreads();  // s is free again
-    return base + x - v;
+    return excl;
 }
 
 constexpr int EN_TILE = 256;  // blocks per tile = lanes per workgroup

@@ -7,23 +7,13 @@
 //   a3d_mask_loss     the 256 -> 1 predictor conv, F.binary_cross_entropy_with_logits(mean) and the backward pass of both, fused so the
 //                     28 x 28 x 256 activation (803 KB per ROI, the head's largest) is read once and its gated gradient written once.
 // Rows are the compacted foreground ROIs [0, *live).  No atomics anywhere: the same bits on every run.
-#include "a3d_common.h"
+#include "kernel_prims.h"
 #include "../../include/a3d.h"
 
 namespace {
 constexpr int MT_THREADS = 256;
 constexpr int MT_WAVES = MT_THREADS / A3D_WAVE;
 constexpr int MT_MAX_GRID = 32768;  // samples per bin on a side: a box beyond 28 x this many pixels is not a proposal of any image
-
-__device__ __forceinline__ float mk_wave_sum(float v) {  // butterfly: every lane ends with the same sum, in a fixed order
-    for (int m = A3D_WAVE / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, A3D_WAVE);
-    return v;
-}
-
-__device__ __forceinline__ int mk_live(const int *live, int rows) {
-    const int nl = __builtin_amdgcn_readfirstlane(*live);
-    return nl < 0 ? 0 : (nl < rows ? nl : rows);
-}
 
 // One bilinear sample of a byte mask: the pooler's out-of-range and border rules (samples outside [-1, H] x [-1, W] are 0; coordinates
 // clamp to the last row / column, so every read is inside the mask).
@@ -54,7 +44,7 @@ __device__ __forceinline__ float mk_bilinear(const uint8_t *__restrict__ p, int 
 __global__ __launch_bounds__(MT_THREADS) void mask_targets_kernel(const a3d_mask_targets_desc d) {
     const int S = d.S;
     const int r = blockIdx.x / S, ph = blockIdx.x - r * S;
-    if (r >= mk_live(d.live, d.rows)) return;
+    if (r >= a3d_live_rows(d.live, d.rows)) return;
     const int wave = threadIdx.x / A3D_WAVE, lane = threadIdx.x % A3D_WAVE;
     int b = 0;
     while (b + 1 < d.B && d.row_offset[b + 1] <= r) ++b;
@@ -95,7 +85,7 @@ __global__ __launch_bounds__(MT_THREADS) void mask_targets_kernel(const a3d_mask
             const float x = xbin + ((float)ix + 0.5f) * bw / (float)gw;
             acc += mk_bilinear(mask, d.H, d.W, y, x);
         }
-        acc = mk_wave_sum(acc);
+        acc = a3d_wave_sum(acc);
         if (lane == 0) out[pw] = acc / cnt >= 0.5f ? 1 : 0;
     }
 }
@@ -112,12 +102,12 @@ constexpr int ML_STRANDS = ML_THREADS / 4;
 // 16-byte loads per lane, four interleaved dot products, and the lane's 4 x 4 values stay in registers until the gated gradient leaves.
 __global__ __launch_bounds__(ML_THREADS) void mask_loss_kernel(const a3d_mask_loss_desc d) {
     __shared__ float part[ML_WAVES][ML_COLS];
-    const int live = mk_live(d.live, d.rows);
+    const int live = a3d_live_rows(d.live, d.rows);
     const int P = d.P, PP = P * P, S2 = 2 * P;
     const long long units = (long long)live * PP;
     const float inv = live > 0 ? 1.f / ((float)live * (float)(4 * PP)) : 0.f;
     const int wave = threadIdx.x / A3D_WAVE, lane = threadIdx.x % A3D_WAVE;
-    const f32x4 w = *reinterpret_cast<const f32x4 *>(d.w + lane * 4);
+    const f32x4 w = a3d_ld4(d.w + lane * 4);
     const float bias = *d.b;
     f32x4 dw = {0.f, 0.f, 0.f, 0.f};
     float db = 0.f, ls = 0.f;
@@ -126,14 +116,11 @@ __global__ __launch_bounds__(ML_THREADS) void mask_loss_kernel(const a3d_mask_lo
         f32x4 y[4];
         float p[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) y[q] = *reinterpret_cast<const f32x4 *>(d.yu + at + q * ML_C);
+        for (int q = 0; q < 4; ++q) y[q] = a3d_ld4(d.yu + at + q * ML_C);
 #pragma unroll
         for (int q = 0; q < 4; ++q) p[q] = __builtin_fmaf(y[q][3], w[3], __builtin_fmaf(y[q][2], w[2], __builtin_fmaf(y[q][1], w[1], y[q][0] * w[0])));
 #pragma unroll
-        for (int m = A3D_WAVE / 2; m > 0; m >>= 1) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) p[q] += __shfl_xor(p[q], m, A3D_WAVE);
-        }
+        for (int q = 0; q < 4; ++q) p[q] = a3d_wave_sum(p[q]);
         const int r = (int)(u / PP), rem = (int)(u - (long long)r * PP), iy = rem / P, ix = rem - iy * P;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -151,7 +138,7 @@ __global__ __launch_bounds__(ML_THREADS) void mask_loss_kernel(const a3d_mask_lo
                 dw[k] = __builtin_fmaf(dz, y[q][k], dw[k]);
                 g[k] = y[q][k] > 0.f ? dz * w[k] : 0.f;  // the deconv's ReLU gate: closed at 0
             }
-            *reinterpret_cast<f32x4 *>(d.dyu + at + q * ML_C) = g;
+            a3d_st4(d.dyu + at + q * ML_C, g);
             if (d.z && lane == 0) d.z[px] = z;
         }
     }
@@ -175,14 +162,11 @@ __global__ __launch_bounds__(ML_THREADS) void mask_loss_reduce_kernel(const a3d_
         for (int k = j; k < ML_WGS; k += ML_STRANDS) s += d.workspace[(size_t)k * ML_COLS + c];
     red[t] = s;
     __syncthreads();
-    for (int w = ML_THREADS / 2; w >= 4; w >>= 1) {  // (t and t + w hold the same column: w is a multiple of 4)
-        if (t < w) red[t] = red[t] + red[t + w];
-        __syncthreads();
-    }
+    a3d_lds_tree<ML_THREADS, 4>(red);  // (t and t + w hold the same column: w is a multiple of 4)
     if (t < 4 && c < ML_C + 2) {
         float v = red[t];
         if (c == ML_C + 1) {  // the mean's divisor: the device live count
-            const int live = mk_live(d.live, d.rows);
+            const int live = a3d_live_rows(d.live, d.rows);
             v = live > 0 ? v * (1.f / ((float)live * (float)(4 * d.P * d.P))) : 0.f;
         }
         d.out[c] = v;

@@ -26,9 +26,9 @@
 //   scan    one block turns the block totals into exclusive offsets and writes `counts`.
 //   emit    one lattice pixel per thread, so neighbouring lanes write neighbouring vertices: slot = block offset + word prefix +
 //           popcount of the lower bits of the word; the rank of the pixel below comes from the same three numbers of ITS word.
-//           The pose table sits in LDS as in project_hypotheses_kernel; the mask is read once for all poses.
+//           The pose table sits in LDS; the mask is read once for all poses.
 // No host synchronisation, vector stores only.
-#include "a3d_common.h"
+#include "kernel_prims.h"
 #include "../../include/a3d.h"
 
 namespace {
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(kBlock) void mesh_live_kernel(const unsigned int *_
     if (l < L) {
         const int ly = l / Lw, lx = l - ly * Lw;
         const int p = ly * s * W + lx * s;  // < H*W: a bit past the mask is never read
-        b = (((bits[p >> 5] >> (p & 31)) & 1u) ^ invert) != 0u;
+        b = (a3d_mask_bit(bits, p) ^ invert) != 0u;
     }
     const unsigned long long m = __ballot(b);
     const int lane = threadIdx.x & (A3D_WAVE - 1);
@@ -78,21 +78,11 @@ __global__ __launch_bounds__(kBlock) void mesh_live_kernel(const unsigned int *_
     if (lane == 32 && w0 + 1 < LW) live[w0 + 1] = (unsigned int)(m >> 32);
 }
 
-__device__ __forceinline__ int wave_inclusive_scan(int v) {
-    const int lane = threadIdx.x & (A3D_WAVE - 1);
-#pragma unroll
-    for (int d = 1; d < A3D_WAVE; d <<= 1) {
-        const int t = __shfl_up(v, d, A3D_WAVE);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-// exclusive scan of (a, b) over the block's 256 threads; ta / tb = the block's totals.  `part` is [2][4] ints of LDS; the caller
-// puts a __syncthreads between two uses of the same array.
+// a3d_block_exclusive_scan of the pair (a, b) behind ONE barrier (two calls of the helper would cost a second one); ta / tb = the
+// block's totals.  `part` is [2][4] ints of LDS; the caller puts a __syncthreads between two uses of the same array.
 __device__ __forceinline__ void block_exclusive_scan2(const int a, const int b, int (*part)[kBlock / A3D_WAVE], int &ea, int &eb, int &ta, int &tb) {
     const int lane = threadIdx.x & (A3D_WAVE - 1), wave = threadIdx.x / A3D_WAVE;
-    const int ia = wave_inclusive_scan(a), ib = wave_inclusive_scan(b);
+    const int ia = a3d_wave_inclusive_scan(a), ib = a3d_wave_inclusive_scan(b);
     if (lane == A3D_WAVE - 1) {
         part[0][wave] = ia;
         part[1][wave] = ib;
@@ -192,25 +182,15 @@ __global__ __launch_bounds__(kBlock) void mesh_emit_kernel(const live_row row, c
     if (k < g.cap_v) {
         uvs[(size_t)k * 2] = (float)((double)x / (double)g.W);
         uvs[(size_t)k * 2 + 1] = (float)(1.0 + (-(double)y) / (double)g.H);
-        // get_pcd in float64, then .float(): as project_hypotheses_kernel
-        const double rx = ((double)x - g.cx) / g.focal, ry = ((double)y - g.cy) / g.focal;
-        const double den = (double)g.normal[0] * rx + (double)g.normal[1] * ry + (double)g.normal[2];
-        const double depth = (double)g.offset / den;
-        const float px = (float)(depth * rx), py = (float)(depth * ry), pz = (float)depth;
-        const float qx = px - g.pivot[0], qy = py - g.pivot[1], qz = pz - g.pivot[2];
+        float pt[3];
+        a3d_plane_lift(x, y, g.focal, g.cx, g.cy, g.normal, g.offset, pt);
         for (int a = 0; a < g.A; ++a) {
-            const float *m = xf[a];
-            const float tx = (m[0] * qx + m[1] * qy + m[2] * qz) + g.pivot[0] + m[9];
-            float ty = (m[3] * qx + m[4] * qy + m[5] * qz) + g.pivot[1] + m[10];
-            float tz = (m[6] * qx + m[7] * qy + m[8] * qz) + g.pivot[2] + m[11];
-            if (g.flip_yz) {
-                ty = -ty;
-                tz = -tz;
-            }
+            float t[3];
+            a3d_pose_apply(xf[a], pt, g.pivot, t);
             float *o = verts + ((size_t)a * g.cap_v + k) * 3;
-            o[0] = tx;
-            o[1] = ty;
-            o[2] = tz;
+            o[0] = t[0];
+            o[1] = g.flip_yz ? -t[1] : t[1];
+            o[2] = g.flip_yz ? -t[2] : t[2];
         }
     }
 
@@ -248,7 +228,7 @@ bool mesh_make_plan(const int H, const int W, const int s, mesh_plan *p) {
     p->Lh = (int)(((long long)H + s - 1) / s);
     p->Lw = (int)(((long long)W + s - 1) / s);
     p->L = p->Lh * p->Lw;
-    p->LW = (p->L + 31) / 32;
+    p->LW = a3d_mask_words((size_t)p->L);
     p->nb = (p->LW + kBlock - 1) / kBlock;
     size_t at = 0;
     const size_t per_word = (size_t)p->LW * 4, per_block = (size_t)p->nb * 8;

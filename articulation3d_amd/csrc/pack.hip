@@ -2,7 +2,7 @@
 // temporal optimiser.  One record = the fields create_instances() materialises for one detection
 // (pkg/utils/arti_vis.py:162-186): box xyxy (4), score, class, plane normal*offset (3), rot axis (3),
 // tran axis (2) and the 28x28 soft mask (re-pasted deterministically by the receiver) = 798 floats.
-#include "a3d_common.h"
+#include "kernel_prims.h"
 #include "../../include/a3d.h"
 
 #define REC_HEAD 14
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(1024) void mask_rle_kernel(const unsigned char *__r
     __shared__ int s_carry;
     const unsigned char *m = masks + (size_t)blockIdx.x * H * W;
     int *out = pos + (size_t)blockIdx.x * cap;
-    const int N = H * W, NW = (N + 31) >> 5;
+    const int N = H * W, NW = a3d_mask_words((size_t)N);
     for (int j = threadIdx.x; j < NW; j += 1024) {
         unsigned w = 0;
         int i = j << 5;
@@ -137,15 +137,8 @@ __global__ __launch_bounds__(1024) void mask_rle_kernel(const unsigned char *__r
             if (valid < 32) t &= (1u << valid) - 1u;
         }
         const int c = __popc(t);
-        int incl = c;
-        for (int off = 1; off < 64; off <<= 1) {
-            const int u = __shfl_up(incl, off, 64);
-            if ((threadIdx.x & 63) >= off) incl += u;
-        }
-        if ((threadIdx.x & 63) == 63) wave_sum[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        int base = s_carry + incl - c;
-        for (int q = 0; q < (int)(threadIdx.x >> 6); ++q) base += wave_sum[q];
+        int pass_total;
+        const int base = s_carry + a3d_block_exclusive_scan<1024>(c, wave_sum, pass_total);
         int k = base;
         while (t) {  // the indices of the set bits, in increasing order
             const int b = __ffs(t) - 1;
@@ -154,7 +147,7 @@ __global__ __launch_bounds__(1024) void mask_rle_kernel(const unsigned char *__r
             ++k;
         }
         __syncthreads();
-        if (threadIdx.x == 1023) s_carry = base + c;
+        if (threadIdx.x == 1023) s_carry = base + c;  // (= the carry + pass_total)
         __syncthreads();
     }
     if (threadIdx.x == 0) {

@@ -13,6 +13,7 @@
 // and the bytes before it and after the last whole group go one by one.  The bits that belong to an aligned group of mask bytes then
 // start anywhere in a word; they come out of the (at most two) words that hold them.  Sums are integers, added with integer atomics
 // (LDS, then one per workgroup and counter on the global counters a first launch zeroes): no result depends on the order of arrival.
+#include "kernel_prims.h"
 #include "eval_common.h"
 
 #include <limits.h>
@@ -55,14 +56,6 @@ __device__ __forceinline__ unsigned pe_nonzero4(unsigned v) {
     return ((t >> 7) * 0x10204080u) >> 28;                                      // bits 0, 8, 16, 24 -> 0, 1, 2, 3 (no two products meet)
 }
 
-// the 16 bits of pixels q .. q + 15 of one row of bits (q + 15 < H * W, so the second word exists whenever it is needed)
-__device__ __forceinline__ unsigned pe_bits16(const unsigned *row, int words, int q) {
-    const int wi = q >> 5, sh = q & 31;
-    unsigned long long w = row[wi];
-    if (sh > 16 && wi + 1 < words) w |= (unsigned long long)row[wi + 1] << 32;
-    return (unsigned)(w >> sh) & 0xFFFFu;
-}
-
 __global__ __launch_bounds__(PE_THREADS) void pe_counts_kernel(const a3d_eval_mask_counts_desc a, const int hw, const int words) {
     __shared__ int s_row, s_slot, s_cnt[2];
     const int tid = threadIdx.x;
@@ -96,7 +89,7 @@ __global__ __launch_bounds__(PE_THREADS) void pe_counts_kernel(const a3d_eval_ma
                 const int j = tid + k * PE_THREADS;
                 if (j < groups) {
                     const unsigned m = pe_nonzero4(v[k].x) | (pe_nonzero4(v[k].y) << 4) | (pe_nonzero4(v[k].z) << 8) | (pe_nonzero4(v[k].w) << 12);
-                    const unsigned g = grow ? pe_bits16(grow, words, b0 + (j << 4)) : 0u;
+                    const unsigned g = grow ? a3d_mask_window<16>(grow, b0 + (j << 4), words) : 0u;
                     inter += __popc(m & g);
                     uni += __popc(m | g);
                 }
@@ -105,15 +98,13 @@ __global__ __launch_bounds__(PE_THREADS) void pe_counts_kernel(const a3d_eval_ma
             if (tid < singles) {
                 const int p = tid < head ? p0 + tid : b1 + (tid - head);
                 const unsigned m = (mrow && mrow[p]) ? 1u : 0u;
-                const unsigned g = grow ? (grow[p >> 5] >> (p & 31)) & 1u : 0u;
+                const unsigned g = grow ? a3d_mask_bit(grow, p) : 0u;
                 inter += m & g;
                 uni += m | g;
             }
         }
-        for (int off = 1; off < A3D_WAVE; off <<= 1) {
-            inter += __shfl_xor(inter, off, A3D_WAVE);
-            uni += __shfl_xor(uni, off, A3D_WAVE);
-        }
+        inter = a3d_wave_sum(inter);
+        uni = a3d_wave_sum(uni);
         if ((tid & (A3D_WAVE - 1)) == 0 && (inter | uni)) {
             atomicAdd(&s_cnt[0], inter);
             atomicAdd(&s_cnt[1], uni);
@@ -203,7 +194,7 @@ extern "C" int a3d_eval_mask_counts(const a3d_eval_mask_counts_desc *d, void *st
     if (d->S > 0 && !d->masks) return A3D_ERR_ARG;
     if (d->N > 0 && (!d->det || !d->det_slot || !d->gt_id || !d->inter || !d->uni)) return A3D_ERR_ARG;
     if (d->I == 0 || d->N == 0) return A3D_OK;
-    const int hw = d->H * d->W, words = (int)(((long long)hw + 31) / 32);
+    const int hw = d->H * d->W, words = a3d_mask_words((size_t)hw);
     a3d_begin();
     hipLaunchKernelGGL(pe_assign_kernel, dim3((d->N + PE_THREADS - 1) / PE_THREADS), dim3(PE_THREADS), 0, (hipStream_t)stream, *d);
     hipLaunchKernelGGL(pe_counts_kernel, dim3((hw - 1) / PE_BLOCK + 1, d->N < 65535 ? d->N : 65535), dim3(PE_THREADS), 0, (hipStream_t)stream,

@@ -7,7 +7,7 @@
 //                   draw = normalise-backward(k sign(pred - gt)),  dh = (h > 0) ? w^T draw : 0,  dw = sum draw x h,  db = sum draw.
 // Rows are the compacted foreground ROIs [0, *live).  *live is known before any row is read, so k needs no first pass.  One wave per row;
 // no atomics anywhere: the same bits on every run.
-#include "a3d_common.h"
+#include "kernel_prims.h"
 #include "../../include/a3d.h"
 
 namespace {
@@ -20,24 +20,7 @@ constexpr int PL_RED_COLS = 16;               // the reduce launch: 16 columns x
 constexpr int PL_RED_STRANDS = PL_THREADS / PL_RED_COLS;
 constexpr float PL_EPS = 1e-12f;              // F.normalize's eps
 
-__device__ __forceinline__ int pl_live(const int *live, int rows) {
-    const int nl = __builtin_amdgcn_readfirstlane(*live);
-    return nl < 0 ? 0 : (nl < rows ? nl : rows);
-}
-
 __device__ __forceinline__ float pl_sign(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }  // (abs backward: 0 at 0)
-
-// d(v / max(|v|, eps)) backward for a 3-vector, axis_train.hip's ax_norm_bwd rule: clamp_min passes the gradient of |v| where
-// |v| >= eps only, so below eps no tangential term passes (there dn == eps)
-__device__ __forceinline__ void pl_norm_bwd(const float v[3], float n, float dn, const float gs[3], float g[3]) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) g[j] = gs[j] / dn;
-    if (n >= PL_EPS) {
-        const float dd = -((gs[0] * v[0] + gs[1] * v[1]) + gs[2] * v[2]) / (dn * dn);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) g[j] += dd * v[j] / n;
-    }
-}
 
 // One wave per row, rows gw, gw + PL_PARTS, ...: the lane holds columns q * 256 + lane * 4 + (0..3), q < NV, of the row and of the three
 // weight rows in registers.  NV independent 16-byte loads, three interleaved dot products folded over the wave by a butterfly (a fixed
@@ -45,7 +28,7 @@ __device__ __forceinline__ void pl_norm_bwd(const float v[3], float n, float dn,
 template <int NV>
 __global__ __launch_bounds__(PL_THREADS) void plane_loss_kernel(const a3d_plane_loss_desc d) {
     constexpr int K = NV * 256;
-    const int live = pl_live(d.live, d.rows);
+    const int live = a3d_live_rows(d.live, d.rows);
     const int lane = threadIdx.x % A3D_WAVE, gw = blockIdx.x * PL_WAVES + threadIdx.x / A3D_WAVE;
     if (gw >= live) return;  // (wave-uniform; the reduce launch reads the partials of the waves [0, min(live, PL_PARTS)) only)
     const float k = d.loss_weight / (float)live;
@@ -54,7 +37,7 @@ __global__ __launch_bounds__(PL_THREADS) void plane_loss_kernel(const a3d_plane_
     for (int j = 0; j < 3; ++j) {
 #pragma unroll
         for (int q = 0; q < NV; ++q) {
-            w[j][q] = *reinterpret_cast<const f32x4 *>(d.w + (size_t)j * K + q * 256 + lane * 4);
+            w[j][q] = a3d_ld4(d.w + (size_t)j * K + q * 256 + lane * 4);
             dw[j][q] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     }
@@ -64,7 +47,7 @@ __global__ __launch_bounds__(PL_THREADS) void plane_loss_kernel(const a3d_plane_
         const size_t at = (size_t)r * K + lane * 4;
         f32x4 h[NV];
 #pragma unroll
-        for (int q = 0; q < NV; ++q) h[q] = *reinterpret_cast<const f32x4 *>(d.h + at + q * 256);
+        for (int q = 0; q < NV; ++q) h[q] = a3d_ld4(d.h + at + q * 256);
         float raw[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
@@ -77,10 +60,7 @@ __global__ __launch_bounds__(PL_THREADS) void plane_loss_kernel(const a3d_plane_
             raw[j] = acc;
         }
 #pragma unroll
-        for (int m = A3D_WAVE / 2; m > 0; m >>= 1) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) raw[j] += __shfl_xor(raw[j], m, A3D_WAVE);
-        }
+        for (int j = 0; j < 3; ++j) raw[j] = a3d_wave_sum(raw[j]);
 #pragma unroll
         for (int j = 0; j < 3; ++j) raw[j] += bias[j];
         if (d.raw && lane == 0) {
@@ -110,7 +90,7 @@ __global__ __launch_bounds__(PL_THREADS) void plane_loss_kernel(const a3d_plane_
                 gs[j] = k * pl_sign(e);
             }
             if (d.normal_only)
-                pl_norm_bwd(raw, n, dn, gs, dr);
+                a3d_norm_bwd<3>(raw, n, dn, PL_EPS, gs, dr);
             else {
 #pragma unroll
                 for (int j = 0; j < 3; ++j) dr[j] = gs[j];
@@ -128,23 +108,23 @@ __global__ __launch_bounds__(PL_THREADS) void plane_loss_kernel(const a3d_plane_
                 const float s = __builtin_fmaf(w[2][q][c], dr[2], __builtin_fmaf(w[1][q][c], dr[1], w[0][q][c] * dr[0]));
                 gh[c] = h[q][c] > 0.f ? s : 0.f;  // the FC's ReLU gate: closed at 0
             }
-            *reinterpret_cast<f32x4 *>(d.dh + at + q * 256) = gh;
+            a3d_st4(d.dh + at + q * 256, gh);
         }
     }
     float *part = d.workspace + (size_t)gw * (3 * K + 4);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
 #pragma unroll
-        for (int q = 0; q < NV; ++q) *reinterpret_cast<f32x4 *>(part + (size_t)j * K + q * 256 + lane * 4) = dw[j][q];
+        for (int q = 0; q < NV; ++q) a3d_st4(part + (size_t)j * K + q * 256 + lane * 4, dw[j][q]);
     }
-    if (lane == 0) *reinterpret_cast<f32x4 *>(part + 3 * K) = f32x4{db[0], db[1], db[2], ls};
+    if (lane == 0) a3d_st4(part + 3 * K, f32x4{db[0], db[1], db[2], ls});
 }
 
 // The partials of the waves that had a row, 16 columns per workgroup: 16 strands sum every 16th partial in order, then a fixed tree.
 __global__ __launch_bounds__(PL_THREADS) void plane_loss_reduce_kernel(const a3d_plane_loss_desc d) {
     __shared__ float red[PL_THREADS];
     const int C = 3 * d.K + 4;
-    const int live = pl_live(d.live, d.rows);
+    const int live = a3d_live_rows(d.live, d.rows);
     const int parts = live < PL_PARTS ? live : PL_PARTS;
     const int t = threadIdx.x, c = blockIdx.x * PL_RED_COLS + (t % PL_RED_COLS), j = t / PL_RED_COLS;
     float s = 0.f;
@@ -152,6 +132,7 @@ __global__ __launch_bounds__(PL_THREADS) void plane_loss_reduce_kernel(const a3d
         for (int p = j; p < parts; p += PL_RED_STRANDS) s += d.workspace[(size_t)p * C + c];
     red[t] = s;
     __syncthreads();
+    // (a3d_lds_tree<PL_THREADS, PL_RED_COLS> written out: through the helper this kernel's exec-mask arithmetic compiles differently)
     for (int w = PL_THREADS / 2; w >= PL_RED_COLS; w >>= 1) {  // (t and t + w hold the same column: w is a multiple of 16)
         if (t < w) red[t] = red[t] + red[t + w];
         __syncthreads();

@@ -30,19 +30,10 @@
 // included).  The frame index and the table cursors are wave-uniform, so layer / piece / instance records come through
 // scalar loads; a wave whose pixel span misses a layer's cull box (one ballot) never touches its pieces or mask word,
 // and one that misses a piece's box skips its half-planes.
-#include "a3d_common.h"
+#include "kernel_prims.h"
 #include "../../include/a3d.h"
 
 namespace {
-
-// the 4 mask bits of pixels p .. p+3 of one bit-packed mask row (bits past the mask's last word read as 0)
-__device__ __forceinline__ unsigned int mask_nibble(const unsigned int *__restrict__ row, const long long p, const int words) {
-    const long long w = p >> 5;
-    const int sh = (int)(p & 31);
-    unsigned int m = row[w] >> sh;
-    if (sh > 28 && w + 1 < words) m |= row[w + 1] << (32 - sh);
-    return m & 0xFu;
-}
 
 // A table record as ONE group of scalar loads.  Left to itself the compiler loads each field where it is first used -- behind the
 // short-circuit of the box test, behind the branch on the kind -- which costs a wave two or three dependent round trips per record; the
@@ -110,7 +101,7 @@ __global__ __launch_bounds__(256) void render_panels_kernel(const unsigned char 
             if (__ballot(in_box) == 0ull) continue;  // the wave's pixel span misses the cull box
             unsigned int cov = 0;
             if (L.kind == A3D_RENDER_MASK) {
-                if (L.p0 >= 0 && L.p0 < d.n_masks) cov = mask_nibble(bits + (size_t)L.p0 * words, p, words);
+                if (L.p0 >= 0 && L.p0 < d.n_masks) cov = a3d_mask_window<4>(bits + (size_t)L.p0 * words, p, words);
             } else {
                 const int p1 = min(L.p1, d.n_pieces);
                 for (int q = max(L.p0, 0); q < p1; ++q) {
@@ -154,7 +145,7 @@ __global__ __launch_bounds__(256) void render_panels_kernel(const unsigned char 
             const int row = inst_row[i];
             if (row < 0 || row >= d.n_masks) continue;
             const float n0 = normals[(size_t)i * 3], n1 = normals[(size_t)i * 3 + 1], n2 = normals[(size_t)i * 3 + 2];
-            const unsigned int m = mask_nibble(bits + (size_t)row * words, p, words);
+            const unsigned int m = a3d_mask_window<4>(bits + (size_t)row * words, p, words);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float b = (float)((m >> j) & 1u);
@@ -206,7 +197,7 @@ extern "C" int a3d_render_panels(const a3d_render_desc *d, void *stream) {
     if (d->F > 0 && (!d->frames || !d->out || !d->layer_off || !d->inst_off)) return A3D_ERR_ARG;
     if (d->F == 0) return A3D_OK;
     const int groups = (d->W + 3) / 4;
-    const int words = (int)(((size_t)d->H * d->W + 31) / 32);
+    const int words = a3d_mask_words((size_t)d->H * d->W);
     // dword accesses need every row start, the panel's first column and its width on a 4-pixel (12-byte) boundary
     const int vec_in = (d->W % 4 == 0) && ((uintptr_t)d->frames % 4 == 0);
     const int vec_out = (d->W % 4 == 0) && (d->pitch % 4 == 0) && (d->col % 4 == 0) && ((uintptr_t)d->out % 4 == 0);

@@ -1,13 +1,8 @@
 // HBM-bound NHWC helpers of the detection path: frame normalisation, the stem max-pool, the FPN
 // p6 subsample, bilinear resizes of the depth head and its 64->1 3x3 prediction conv.
 // One thread owns one float4 of channels (16 B/lane, coalesced); grid-stride loops capped at 2048 WGs.
-#include "a3d_common.h"
+#include "kernel_prims.h"
 #include "../../include/a3d.h"
-
-static inline int grid_for(size_t n) {
-    size_t b = (n + 255) / 256;
-    return (int)(b > 2048 ? 2048 : (b ? b : 1));
-}
 
 // ---- (x - mean)/std, uint8 HWC BGR -> fp32 NHWC4 ------------------------------------------------
 __global__ __launch_bounds__(256) void preprocess_u8_kernel(const uint8_t *__restrict__ in, float *__restrict__ out,
@@ -37,7 +32,7 @@ extern "C" int a3d_preprocess_u8hwc(const uint8_t *frames, float *out, int B, in
     if (!frames || !out || B <= 0 || H <= 0 || W <= 0) return A3D_ERR_ARG;
     const size_t npix = (size_t)B * H * W;
     a3d_begin();
-    hipLaunchKernelGGL(preprocess_u8_kernel, dim3(grid_for(npix)), dim3(256), 0, (hipStream_t)stream, frames, out, npix,
+    hipLaunchKernelGGL(preprocess_u8_kernel, dim3(a3d_stream_grid(npix)), dim3(256), 0, (hipStream_t)stream, frames, out, npix,
                        mean[0], mean[1], mean[2], std[0], std[1], std[2]);
     return a3d_check_launch();
 }
@@ -47,7 +42,7 @@ extern "C" int a3d_preprocess_f32chw(const float *images, float *out, int B, int
     if (!images || !out || B <= 0 || H <= 0 || W <= 0) return A3D_ERR_ARG;
     const size_t hw = (size_t)H * W;
     a3d_begin();
-    hipLaunchKernelGGL(preprocess_chw_kernel, dim3(grid_for(hw * B)), dim3(256), 0, (hipStream_t)stream, images, out, B,
+    hipLaunchKernelGGL(preprocess_chw_kernel, dim3(a3d_stream_grid(hw * B)), dim3(256), 0, (hipStream_t)stream, images, out, B,
                        hw, mean[0], mean[1], mean[2], std[0], std[1], std[2]);
     return a3d_check_launch();
 }
@@ -115,7 +110,7 @@ extern "C" int a3d_preprocess_resize_u8(const uint8_t *frames, float *out, uint8
     if (!frames || !out || B <= 0 || Hs <= 0 || Ws <= 0 || Hd <= 0 || Wd <= 0) return A3D_ERR_ARG;
     const size_t npix = (size_t)B * Hd * Wd;
     a3d_begin();
-    hipLaunchKernelGGL(preprocess_resize_u8_kernel, dim3(grid_for(npix)), dim3(256), 0, (hipStream_t)stream, frames, out, out_u8, B, Hs,
+    hipLaunchKernelGGL(preprocess_resize_u8_kernel, dim3(a3d_stream_grid(npix)), dim3(256), 0, (hipStream_t)stream, frames, out, out_u8, B, Hs,
                        Ws, Hd, Wd, swap_rb, mean[0], mean[1], mean[2], std[0], std[1], std[2]);
     return a3d_check_launch();
 }
@@ -151,7 +146,7 @@ extern "C" int a3d_maxpool3x3s2_nhwc(const float *x, float *y, int B, int H, int
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     const size_t total = (size_t)B * Ho * Wo * (C / 4);
     a3d_begin();
-    hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W,
+    hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(a3d_stream_grid(total)), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W,
                        C / 4, Ho, Wo);
     return a3d_check_launch();
 }
@@ -177,21 +172,12 @@ extern "C" int a3d_subsample2_nhwc(const float *x, float *y, int B, int H, int W
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const size_t total = (size_t)B * Ho * Wo * (C / 4);
     a3d_begin();
-    hipLaunchKernelGGL(subsample2_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, C / 4,
+    hipLaunchKernelGGL(subsample2_kernel, dim3(a3d_stream_grid(total)), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, C / 4,
                        Ho, Wo);
     return a3d_check_launch();
 }
 
 // ---- bilinear resize, align_corners=False (aten upsample_bilinear2d semantics) -------------------
-__device__ __forceinline__ void src_index(int o, float scale, int in_size, int &i0, int &i1, float &l1) {
-    float s = scale * ((float)o + 0.5f) - 0.5f;
-    if (s < 0.f) s = 0.f;
-    i0 = (int)s;
-    if (i0 > in_size - 1) i0 = in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = s - (float)i0;
-}
-
 template <int VEC>
 __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float *__restrict__ x, float *__restrict__ y, int B,
                                                               int H, int W, int C, int Ho, int Wo, float sh, float sw) {
@@ -206,8 +192,8 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float *__res
         const int b = (int)(p / Ho);
         int y0, y1, x0, x1;
         float ly, lx;
-        src_index(oh, sh, H, y0, y1, ly);
-        src_index(ow, sw, W, x0, x1, lx);
+        a3d_src_index(oh, sh, H, y0, y1, ly);
+        a3d_src_index(ow, sw, W, x0, x1, lx);
         const float hy = 1.f - ly, hx = 1.f - lx;
         const float *base = x + (size_t)b * H * W * C + c;
         for (int k = 0; k < VEC; ++k) {
@@ -232,7 +218,7 @@ __global__ __launch_bounds__(256) void resize_bilinear_c1x4_kernel(const float *
         const int b = (int)(p / Ho);
         int y0, y1;
         float ly;
-        src_index(oh, sh, H, y0, y1, ly);
+        a3d_src_index(oh, sh, H, y0, y1, ly);
         const float hy = 1.f - ly;
         const float *r0 = x + ((size_t)b * H + y0) * W, *r1 = x + ((size_t)b * H + y1) * W;
         f32x4 o;
@@ -240,7 +226,7 @@ __global__ __launch_bounds__(256) void resize_bilinear_c1x4_kernel(const float *
         for (int k = 0; k < 4; ++k) {
             int x0, x1;
             float lx;
-            src_index(ow0 + k, sw, W, x0, x1, lx);
+            a3d_src_index(ow0 + k, sw, W, x0, x1, lx);
             const float hx = 1.f - lx;
             o[k] = hy * (hx * r0[x0] + lx * r0[x1]) + ly * (hx * r1[x0] + lx * r1[x1]);
         }
@@ -255,14 +241,14 @@ extern "C" int a3d_resize_bilinear_nhwc(const float *x, float *y, int B, int H, 
     a3d_begin();
     if ((C & 3) == 0) {
         const size_t total = (size_t)B * Ho * Wo * (C / 4);
-        hipLaunchKernelGGL(resize_bilinear_kernel<4>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, y, B,
+        hipLaunchKernelGGL(resize_bilinear_kernel<4>, dim3(a3d_stream_grid(total)), dim3(256), 0, (hipStream_t)stream, x, y, B,
                            H, W, C, Ho, Wo, sh, sw);
     } else if (C == 1 && (Wo & 3) == 0 && ((size_t)y & 15) == 0) {
-        hipLaunchKernelGGL(resize_bilinear_c1x4_kernel, dim3(grid_for((size_t)B * Ho * (Wo >> 2))), dim3(256), 0, (hipStream_t)stream, x, y, B,
+        hipLaunchKernelGGL(resize_bilinear_c1x4_kernel, dim3(a3d_stream_grid((size_t)B * Ho * (Wo >> 2))), dim3(256), 0, (hipStream_t)stream, x, y, B,
                            H, W, Ho, Wo, sh, sw);
     } else {
         const size_t total = (size_t)B * Ho * Wo * C;
-        hipLaunchKernelGGL(resize_bilinear_kernel<1>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, y, B,
+        hipLaunchKernelGGL(resize_bilinear_kernel<1>, dim3(a3d_stream_grid(total)), dim3(256), 0, (hipStream_t)stream, x, y, B,
                            H, W, C, Ho, Wo, sh, sw);
     }
     return a3d_check_launch();
@@ -337,8 +323,8 @@ __global__ __launch_bounds__(256) void conv3x3_to1_kernel(const float *__restric
             if (oh0 + q >= H) continue;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float a = acc[q][j];
-                for (int off = lanes_per_pix >> 1; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
+                float a = acc[q][j];  // (a3d_wave_sum's butterfly over the pixel's lanes only: the width is a run-time value here)
+                for (int off = lanes_per_pix >> 1; off > 0; off >>= 1) a += __shfl_xor(a, off, A3D_WAVE);
                 if (sub == 0 && ow0 + j < W) y[((size_t)b * H + oh0 + q) * W + ow0 + j] = a + bias;
             }
         }
@@ -418,9 +404,9 @@ extern "C" int a3d_tapsum9(const float *g, float bias, float *y, int B, int H, i
     if (!g || !y || B <= 0 || H <= 0 || W <= 0) return A3D_ERR_ARG;
     a3d_begin();
     if ((W & 3) == 0 && (((size_t)g | (size_t)y) & 15) == 0)
-        hipLaunchKernelGGL(tapsum9x4_kernel, dim3(grid_for((size_t)B * H * (W >> 2))), dim3(256), 0, (hipStream_t)stream, g, bias, y, B, H, W);
+        hipLaunchKernelGGL(tapsum9x4_kernel, dim3(a3d_stream_grid((size_t)B * H * (W >> 2))), dim3(256), 0, (hipStream_t)stream, g, bias, y, B, H, W);
     else
-        hipLaunchKernelGGL(tapsum9_kernel, dim3(grid_for((size_t)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, bias, y, B, H, W);
+        hipLaunchKernelGGL(tapsum9_kernel, dim3(a3d_stream_grid((size_t)B * H * W)), dim3(256), 0, (hipStream_t)stream, g, bias, y, B, H, W);
     return a3d_check_launch();
 }
 
@@ -442,8 +428,8 @@ __global__ __launch_bounds__(256) void absmax_rows_kernel(const float *__restric
             for (size_t i = head + (n4 << 2) + threadIdx.x; i < n; i += blockDim.x) m = fmaxf(m, a3d_finite_mag(row[i]));
         }
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-        if ((threadIdx.x & 63) == 0 && m > out[b]) atomicMax(reinterpret_cast<int *>(out + b), __float_as_int(m));
+        for (int off = A3D_WAVE / 2; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, A3D_WAVE));
+        if ((threadIdx.x & (A3D_WAVE - 1)) == 0 && m > out[b]) atomicMax(reinterpret_cast<int *>(out + b), __float_as_int(m));
     }
 }
 

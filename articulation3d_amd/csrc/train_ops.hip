@@ -7,6 +7,7 @@
 // All of these are HBM-bound element / row kernels; built with -ffp-contract=off so IoU and delta arithmetic round like
 // the reference's separate mul/add/div (the matcher's labels are compared bit-exactly).
 #include "conv_prims.h"
+#include "kernel_prims.h"
 #include "../../include/a3d.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -471,13 +472,7 @@ __global__ __launch_bounds__(256) void rpn_loss_kernel(const a3d_rpn_loss_desc d
     r0[threadIdx.x] = lc;
     r1[threadIdx.x] = ll;
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) {
-            r0[threadIdx.x] += r0[threadIdx.x + s];
-            r1[threadIdx.x] += r1[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    a3d_lds_tree<256>(r0, r1);
     if (threadIdx.x == 0) {
         partials[(size_t)(part_off + blockIdx.x) * 2 + 0] = r0[0];
         partials[(size_t)(part_off + blockIdx.x) * 2 + 1] = r1[0];
@@ -567,13 +562,7 @@ __global__ __launch_bounds__(256) void box_loss_kernel(const a3d_box_loss_desc d
     r0[threadIdx.x] = lc;
     r1[threadIdx.x] = lb;
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) {
-            r0[threadIdx.x] += r0[threadIdx.x + s];
-            r1[threadIdx.x] += r1[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    a3d_lds_tree<256>(r0, r1);
     if (threadIdx.x == 0) {
         partials[(size_t)blockIdx.x * 2 + 0] = r0[0] * inv;  // (normalised here: the live row count lives on the device)
         partials[(size_t)blockIdx.x * 2 + 1] = r1[0] * inv;
