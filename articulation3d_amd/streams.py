@@ -84,6 +84,45 @@ def _tensors(o):
             yield from _tensors(x)
 
 
+def hop(owner, stream, reads, events, fn, done: bool = False, fork: bool = True):
+    """fn() on `stream`, behind everything enqueued so far on the stream `owner` enqueues on (`owner._cur_stream`, which names `stream`
+    while fn runs -- a hop made inside fn forks from it -- and the old stream again afterwards, also when fn raises).  `reads`: the
+    tensors of the current stream that fn reads (the allocator must not hand their blocks out under the other stream); `events()`: a
+    reusable ordering event per call (a wait captures the record in front of it, so re-recording next step is safe).  fork=False: no
+    fork event -- `stream` already holds everything fn needs, or fn waits for finer events of its own.  done=True -> (fn(), an event
+    recorded behind fn's launches): the caller waits for it, then marks what fn allocated with `adopt`.  `stream` None: fn() inline,
+    the event is None.
+    A plain function with set_stream, no context manager: the 2-image training step is host-bound and makes ~70 hops
+    (`with torch.cuda.stream(...)` costs 65 us per hop on the host, this ~25)."""
+    if stream is None:
+        return (fn(), None) if done else fn()
+    back = owner._cur_stream
+    if fork:
+        ev = events()
+        ev.record(back)
+    for t in reads:
+        t.record_stream(stream)
+    torch.cuda.set_stream(stream)
+    owner._cur_stream = stream
+    try:
+        if fork:
+            stream.wait_event(ev)
+        if not done:
+            return fn()
+        out, ev = fn(), events()
+        ev.record(stream)
+        return out, ev
+    finally:
+        torch.cuda.set_stream(back)
+        owner._cur_stream = back
+
+
+def adopt(tensors, stream) -> None:
+    """What a hop allocated on its side stream is consumed (and later freed) on `stream`: call behind the wait for the hop's event."""
+    for t in tensors:
+        t.record_stream(stream)
+
+
 def run_branches(fns: Sequence[Callable[[], object]], concurrent: bool) -> List[object]:
     """Evaluate independent thunks; with `concurrent` the first runs on the current stream and the others on side streams
     that start behind everything enqueued so far and are joined before returning.  Inputs must stay referenced by the

@@ -29,15 +29,18 @@ from __future__ import annotations
 import math
 import os
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib, ops, train_ops as T
 from .parallel import GradientExchange, allreduce_gradients
 from .ops import ACT_NONE, ACT_RELU, PackedConv
+from .streams import adopt, hop, side as side_stream
 
 FPN_STRIDES = {"p2": 4, "p3": 8, "p4": 16, "p5": 32, "p6": 64}
+LEVELS = tuple(FPN_STRIDES)  # the RPN's levels; the ROI pooler reads the first four
+ROI_SCALES = [1.0 / FPN_STRIDES[n] for n in LEVELS[:4]]
 # One launch for all data-gradient filters and one for all weight-gradient slice reductions of a step instead of one per layer (round 4;
 # "0": the per-layer launches -- the same bits either way, tests/test_gpu_training.py).
 BATCHED_LAUNCHES = os.environ.get("A3D_TRAIN_BATCHED", "1") != "0"
@@ -144,6 +147,82 @@ class _Layer:
         return p
 
 
+class FlatLayout(NamedTuple):
+    layers: Dict[str, Tuple[int, int, int, int]]  # name -> (weight offset, weights, bias offset, biases)
+    tail: Dict[str, Tuple[int, int]]  # name -> (offset, length): what follows the layers
+    total: int  # padded to a multiple of 4
+    segments: list  # [(begin, end)]: the gradient-exchange segments
+
+
+def flat_layout(layers: Sequence[_Layer], bias_rows: Optional[Dict[str, int]] = None, tail: Sequence[Tuple[str, int]] = (),
+                cuts: Sequence[str] = ()) -> FlatLayout:
+    """Where everything lies in the flat buffers: per layer its weights then its biases, in table order, then the tail entries.  A layer
+    has `rows` biases unless `bias_rows` names another count; a new gradient-exchange segment begins at every layer named in `cuts`.
+    Allocates nothing."""
+    out, ends, off = {}, [0], 0
+    for ly in layers:
+        if ly.name in cuts:
+            assert off % 4 == 0
+            ends.append(off)
+        nw, nb = ly.rows * ly.k * ly.k * ly.cin, (bias_rows or {}).get(ly.name, ly.rows)
+        out[ly.name] = (off, nw, off + nw, nb)
+        off += nw + nb
+    tails = {}
+    for name, n in tail:
+        tails[name] = (off, n)
+        off += n
+    ends.append((off + 3) // 4 * 4)
+    return FlatLayout(out, tails, ends[-1], list(zip(ends[:-1], ends[1:])))
+
+
+def detector_layer_table(num_classes: int) -> dict:
+    """The detector's 55 trainable layers in flat-buffer (= forward) order, as the arguments of `flat_layout`: res3-res5 (their FrozenBN
+    folded into constants: no bias entries), the FPN, the RPN head, the box head and predictor.  Gradient-exchange segments: res3 | res4 |
+    res5 + FPN + RPN head | box head -- the backward pass completes them back to front (DetectorTrainer.grad_segments)."""
+    layers, bu, cin = [], "backbone.bottom_up.", 256
+    for name, nblk, mid, cout in RES_STAGES:
+        for i in range(nblk):
+            p, s = f"{bu}{name}.{i}.", 2 if i == 0 else 1
+            layers += [_Layer(p + "conv1", mid, cin, 1, s, 0, ACT_RELU), _Layer(p + "conv2", mid, mid, 3, 1, 1, ACT_RELU),
+                       _Layer(p + "conv3", cout, mid, 1, 1, 0, ACT_RELU)]
+            if i == 0:
+                layers.append(_Layer(p + "shortcut", cout, cin, 1, s, 0, ACT_NONE))
+            cin = cout
+    bn = {ly.name: 0 for ly in layers}
+    for l, c in ((2, 256), (3, 512), (4, 1024), (5, 2048)):
+        layers += [_Layer(f"backbone.fpn_lateral{l}", 256, c, 1, 1, 0, ACT_NONE), _Layer(f"backbone.fpn_output{l}", 256, 256, 3, 1, 1, ACT_NONE)]
+    rp, bh, bp, K = "proposal_generator.rpn_head.", "roi_heads.box_head.", "roi_heads.box_predictor.", num_classes
+    layers += [_Layer(rp + "conv", 256, 256, 3, 1, 1, ACT_RELU),
+               _Layer(rp + "pred", 32, 256, 1, 1, 0, ACT_NONE, sources=[(rp + "objectness_logits", 0, 3), (rp + "anchor_deltas", 3, 12)]),
+               _Layer(bh + "fc1", 1024, 256 * 49, 1, 1, 0, ACT_RELU), _Layer(bh + "fc2", 1024, 1024, 1, 1, 0, ACT_RELU),
+               _Layer(bp + "pred", 32, 1024, 1, 1, 0, ACT_NONE, sources=[(bp + "cls_score", 0, K + 1), (bp + "bbox_pred", K + 1, 4 * K)])]
+    return dict(layers=layers, bias_rows=bn, cuts=(bu + "res4.0.conv1", bu + "res5.0.conv1", bh + "fc1"))
+
+
+def open_exchange(tr, exchange: bool, **kw) -> bool:
+    """In front of a trainer's backward launches: with `exchange` (and unless tr.grad_overlap is "0") the segmented gradient exchange over
+    tr.grads / tr.grad_segments is built on first use (`kw`: GradientExchange's further arguments) and begun -> whether it is live, i.e.
+    whether the step has segments to announce and `optimizer_step` has to finish it."""
+    if not exchange or tr.grad_overlap == "0":
+        return False
+    if tr._xchg is None:
+        tr._xchg = GradientExchange(tr.grads, tr.grad_segments, tr.pg, tr.grad_payload, force=tr.grad_overlap.startswith("force"), **kw)
+    if tr._xchg.active:
+        tr._xchg.begin()
+    return tr._xchg.active
+
+
+class _Rois(NamedTuple):
+    """The sampled ROI set of a step: fixed-size [B, roi_batch_per_image] tensors, slots past count[b] are zero rows."""
+    boxes: torch.Tensor
+    gt: torch.Tensor      # the matched ground-truth box per row
+    cls: torch.Tensor     # its class (num_classes: background)
+    index: torch.Tensor   # the row's index among proposals + ground truth (-1: dead slot)
+    count: torch.Tensor   # [B] live rows
+    proposals: tuple      # (boxes, counts) as the RPN selected them
+    match: torch.Tensor   # matched ground-truth index of every proposal
+
+
 class DetectorTrainer:
     """One training step of the step1_bbox configuration: losses, gradients and the SGD update, all on the device.
 
@@ -184,58 +263,38 @@ class DetectorTrainer:
         self.pixel_mean, self.pixel_std = model.pixel_mean, model.pixel_std
         self.cell_anchors = model.proposal_generator.anchor_generator.cell_anchors
         self.strides = [FPN_STRIDES[n] for n in ("p2", "p3", "p4", "p5", "p6")]
+        # (side streams 0 and 1 of the package's one pool -- streams.side: which hardware queue a stream lands on follows from the order
+        # in which a process first uses its streams, and the step's time with it)
+        self._wg_stream = side_stream(0, self.dev) if WGRAD_SIDE_STREAM else None
+        self._rpn_stream = side_stream(1, self.dev) if RPN_BWD_STREAM else None
         self._build_layers(sd)
         self._anchors_cache: Dict[Tuple[int, int], torch.Tensor] = {}
+        self._anchor = torch.zeros((), device=self.dev, requires_grad=True)  # (autograd_anchor)
+        # every layer's data-gradient filter in one launch, every parked slice reduction of the weight gradients in one (BATCHED_LAUNCHES)
+        self._tbatch = T.TransposeBatch([(ly.w, ly.scale, ly.wt, ly.rows, ly.k, ly.k, ly.cin) for ly in self.layers.values()], self.dev)
+        self._defer = T.DeferredReduces(self.dev)
+        self._frozen_prepared = False  # frozen_forward: the filters of the (unchanged) parameters are there
+        # per step (_begin_step): the stream the step is being enqueued on (streams.hop keeps it), the reusable ordering events and how many
+        # of them the step has taken, the segments a "late" exchange still has to announce
+        self._cur_stream: Optional[torch.cuda.Stream] = None
+        self._wg_events: List[torch.cuda.Event] = []
+        self._wg_calls = 0
+        self._late: List[int] = []
 
     # ------------------------------------------------------------------------------------------ parameters
     def _build_layers(self, sd):
-        L: Dict[str, _Layer] = {}
-        bu = "backbone.bottom_up."
-
-        def bn_fold(prefix):
-            n = prefix + ".norm."
-            scale, shift = ops.fold_bn(sd[n + "weight"], sd[n + "bias"], sd[n + "running_mean"], sd[n + "running_var"], 1e-5)
-            return scale.to(self.dev).contiguous(), shift.to(self.dev).contiguous()
-
-        cin = 256
-        for name, nblk, mid, cout in RES_STAGES:
-            for i in range(nblk):
-                p = f"{bu}{name}.{i}."
-                s = 2 if i == 0 else 1
-                specs = [("conv1", mid, cin, 1, s, 0, ACT_RELU), ("conv2", mid, mid, 3, 1, 1, ACT_RELU), ("conv3", cout, mid, 1, 1, 0, ACT_RELU)]
-                if i == 0:
-                    specs.append(("shortcut", cout, cin, 1, s, 0, ACT_NONE))
-                for cn, rows, ci, k, st, pad, act in specs:
-                    ly = _Layer(p + cn, rows, ci, k, st, pad, act)
-                    ly.scale, ly.shift = bn_fold(p + cn)
-                    L[ly.name] = ly
-                cin = cout
-        for l, c in ((2, 256), (3, 512), (4, 1024), (5, 2048)):
-            L[f"backbone.fpn_lateral{l}"] = _Layer(f"backbone.fpn_lateral{l}", 256, c, 1, 1, 0, ACT_NONE)
-            L[f"backbone.fpn_output{l}"] = _Layer(f"backbone.fpn_output{l}", 256, 256, 3, 1, 1, ACT_NONE)
-        rp = "proposal_generator.rpn_head."
-        L[rp + "conv"] = _Layer(rp + "conv", 256, 256, 3, 1, 1, ACT_RELU)
-        L[rp + "pred"] = _Layer(rp + "pred", 32, 256, 1, 1, 0, ACT_NONE,
-                                sources=[(rp + "objectness_logits", 0, 3), (rp + "anchor_deltas", 3, 12)])
-        bh = "roi_heads.box_head."
-        L[bh + "fc1"] = _Layer(bh + "fc1", 1024, 256 * 49, 1, 1, 0, ACT_RELU)
-        L[bh + "fc2"] = _Layer(bh + "fc2", 1024, 1024, 1, 1, 0, ACT_RELU)
-        bp = "roi_heads.box_predictor."
-        K = self.s.num_classes
-        L[bp + "pred"] = _Layer(bp + "pred", 32, 1024, 1, 1, 0, ACT_NONE, sources=[(bp + "cls_score", 0, K + 1), (bp + "bbox_pred", K + 1, 4 * K)])
-        self.layers = L
-        # (side streams 0 and 1 of the package's one pool -- streams.side: which hardware queue a stream lands on follows from the order
-        # in which a process first uses its streams, and the step's time with it)
-        from .streams import side
-        self._wg_stream = side(0, self.dev) if WGRAD_SIDE_STREAM else None
-        self._rpn_stream = side(1, self.dev) if RPN_BWD_STREAM else None
-        has_bias = lambda ly: ly.scale is None
-        n = sum(ly.rows * ly.k * ly.k * ly.cin + (ly.rows if has_bias(ly) else 0) for ly in L.values())
-        n = (n + 3) // 4 * 4
+        table = detector_layer_table(self.s.num_classes)
+        self.layout = lay = flat_layout(**table)
+        self.layers = L = {ly.name: ly for ly in table["layers"]}
+        for ly in L.values():
+            if lay.layers[ly.name][3] == 0:  # no bias entries: the layer's FrozenBN, folded into constants
+                n = ly.name + ".norm."
+                scale, shift = ops.fold_bn(sd[n + "weight"], sd[n + "bias"], sd[n + "running_mean"], sd[n + "running_var"], 1e-5)
+                ly.scale, ly.shift = scale.to(self.dev).contiguous(), shift.to(self.dev).contiguous()
+        n, nw = lay.total, sum(w for _, w, _, _ in lay.layers.values())
         self.params = torch.zeros(n, device=self.dev)
         self.grads = torch.zeros(n, device=self.dev)
         self.momentum = torch.zeros(n, device=self.dev)
-        nw = sum(ly.rows * ly.k * ly.k * ly.cin for ly in L.values())
         self._wt = torch.empty(nw, device=self.dev)
         nu = sum(16 * ly.rows * ly.cin for ly in L.values() if ly.k == 3)
         self._U = torch.empty(nu, device=self.dev)
@@ -244,19 +303,17 @@ class DetectorTrainer:
         # the same flat layouts -- what csrc/conv_bf16w.hip DMAs (every filter starts at a multiple of 8 elements: 16-byte aligned)
         self._p16 = torch.empty(n, device=self.dev, dtype=torch.bfloat16) if self.prec == 1 else None
         self._wt16 = torch.empty(nw, device=self.dev, dtype=torch.bfloat16) if self.prec == 1 else None
-        off = woff = uoff = 0
+        woff = uoff = 0
         for ly in L.values():
-            nwl = ly.rows * ly.k * ly.k * ly.cin
+            off, nwl, ob, nb = lay.layers[ly.name]
             ly.w = self.params[off:off + nwl].view(ly.rows, -1)
             ly.dw = self.grads[off:off + nwl].view(ly.rows, -1)
             if self._p16 is not None:
                 assert off % 8 == 0 and woff % 8 == 0
                 ly.wb = self._p16[off:off + nwl].view(ly.rows, -1)
                 ly.wtb = self._wt16[woff:woff + nwl].view(ly.cin, -1)
-            off += nwl
-            if has_bias(ly):
-                ly.b, ly.db = self.params[off:off + ly.rows], self.grads[off:off + ly.rows]
-                off += ly.rows
+            if nb:
+                ly.b, ly.db = self.params[ob:ob + nb], self.grads[ob:ob + nb]
             ly.wt = self._wt[woff:woff + nwl].view(ly.cin, -1)
             woff += nwl
             if ly.k == 3:
@@ -264,20 +321,11 @@ class DetectorTrainer:
                 ly.U = self._U[uoff:uoff + nul].view(16, ly.rows, ly.cin)
                 ly.Ut = self._Ut[uoff:uoff + nul].view(16, ly.cin, ly.rows)
                 uoff += nul
-        # Gradient-exchange segments in the order the backward pass completes them.  The flat buffer is in forward order (res3, res4, res5,
-        # FPN, RPN head, box head), the backward pass walks it back to front, so the segments are contiguous ranges taken from the end.
-        first = {}
-        o = 0
-        for ly in L.values():
-            first.setdefault("box" if ly.name.startswith("roi_heads.") else "fpn" if not ly.name.startswith("backbone.bottom_up.")
-                             else ly.name.split(".")[2], o)
-            o += ly.rows * ly.k * ly.k * ly.cin + (ly.rows if has_bias(ly) else 0)
-        cuts = [first["res3"], first["res4"], first["res5"], first["box"], n]
-        assert cuts[0] == 0 and first["res5"] < first["fpn"] < first["box"] and all(a < b and a % 4 == 0 for a, b in zip(cuts, cuts[1:])), cuts
-        # box head (13.9 M, final 0.3 ms into the backward pass) | res5 + FPN + RPN head (19.1 M) | res4 (7.1 M) | res3 (1.2 M: the only
-        # piece whose transfer nothing can hide -- 2.4 MB of bf16).  Four, not more: at the reference's 2 images per GPU every collective
-        # costs ~70 us of host time on a step whose host side is nearly as long as its GPU side.
-        self.grad_segments = [(cuts[i], cuts[i + 1]) for i in (3, 2, 1, 0)]
+        # Gradient-exchange segments in the order the backward pass completes them: the flat buffer is in forward order, the backward pass
+        # walks it back to front.  box head (13.9 M, final 0.3 ms into the backward pass) | res5 + FPN + RPN head (19.1 M) | res4 (7.1 M) |
+        # res3 (1.2 M: the only piece whose transfer nothing can hide -- 2.4 MB of bf16).  Four, not more: at the reference's 2 images per
+        # GPU every collective costs ~70 us of host time on a step whose host side is nearly as long as its GPU side.
+        self.grad_segments = lay.segments[::-1]
         self.load_state_dict(sd)
 
     def _views(self, ly: _Layer, sd_like: bool, buf_w, buf_b):
@@ -343,10 +391,8 @@ class DetectorTrainer:
     def _prepare_filters(self):
         """Per step: data-gradient filters (and the Winograd images of the 3x3 filters) of the CURRENT weights."""
         if BATCHED_LAUNCHES:  # every layer's data-gradient filter in one launch (50 launches of ~6 us each otherwise)
-            if getattr(self, "_tbatch", None) is None:
-                self._tbatch = T.TransposeBatch([(ly.w, ly.scale, ly.wt, ly.rows, ly.k, ly.k, ly.cin) for ly in self.layers.values()], self.dev)
             self._tbatch.run()
-        if not BATCHED_LAUNCHES:
+        else:
             for ly in self.layers.values():
                 T.weight_transpose(ly.w, ly.wt, ly.rows, ly.k, ly.k, ly.cin, scale=ly.scale)
         if self._p16 is not None:  # (bf16 step: both filter sets rounded to bf16, nearest even -- what the kernels' loaders round to)
@@ -379,22 +425,8 @@ class DetectorTrainer:
         data-gradient chain: at the reference's 2 images per GPU every launch of the step is a fraction of a round of the chip, and the
         ~60 weight-gradient launches hide under the chain.  Same kernels in the same order on ONE side stream (the RPN head's five
         accumulating launches stay ordered): the step's gradients keep their bits."""
-        side = self._wg_stream
-        if side is None:
-            return self._wgrad_now(ly, x, dy, accumulate)
-        # (host cost matters: the 2-image step is host-bound.  One reusable event per call site of the step, set_stream instead of the
-        # `with torch.cuda.stream(...)` context manager -- 65 -> ~25 us per weight gradient on the host)
-        main = self._cur_stream  # (the stream this call is made on: the main one, or the RPN head's)
-        ev = self._next_event()
-        ev.record(main)
-        x.record_stream(side)
-        dy.record_stream(side)
-        torch.cuda.set_stream(side)
-        try:
-            side.wait_event(ev)
-            self._wgrad_now(ly, x, dy, accumulate)
-        finally:
-            torch.cuda.set_stream(main)
+        # (forks from the stream this call is made on: the main one, or the RPN head's)
+        hop(self, self._wg_stream, (x, dy), self._next_event, lambda: self._wgrad_now(ly, x, dy, accumulate))
 
     def _next_event(self):
         """A reusable ordering event (one per call site of the step; a wait captures the record in front of it, so re-recording is safe)."""
@@ -404,51 +436,29 @@ class DetectorTrainer:
             self._wg_events.append(torch.cuda.Event())
         return self._wg_events[i]
 
-    def _rpn_head_backward(self, names, dheads, t, feats, st, dP=None):
-        """Data and weight gradients of the RPN head (filters shared by the five levels: weight gradients accumulate in level order).
-        dP given: the serial form -- every level's gradient is added to dP[level] (p6's to p5 through the stride-2 subsample) and None is
-        returned.  dP None: the early form -- returns ({level: gradient}, dp6) for the caller to combine."""
-        L, rp = self.layers, "proposal_generator.rpn_head."
-        out, dp6 = {}, None
-        for li, n in enumerate(names):
-            dt = self._conv(dheads[li], L[rp + "pred"].bwd(), gate=t[li], out_dtype=st)
-            self._wgrad(L[rp + "pred"], t[li], dheads[li], accumulate=li > 0)
-            self._wgrad(L[rp + "conv"], feats[n], dt, accumulate=li > 0)
-            if n == "p6":
-                dp6 = self._conv(dt, L[rp + "conv"].bwd(), wino=False)
-                if dP is not None:
-                    T.zero_insert2(dp6, dP["p5"].shape[1], dP["p5"].shape[2], out=dP["p5"], accumulate=True)
-            elif dP is not None:
-                self._conv(dt, L[rp + "conv"].bwd(), res=dP[n], out=dP[n], wino=False)
-            else:
-                out[n] = self._conv(dt, L[rp + "conv"].bwd(), wino=False)
-        return None if dP is not None else (out, dp6)
+    def _wgrad_now(self, ly: _Layer, x, dy, accumulate=False):
+        # The slice reductions of the step's weight gradients are folded in ONE launch at the end of the backward pass (self._defer.flush()
+        # in _finish_backward): 63 reduce launches of ~17 us each were 11 % of the step at the reference's 2 images per GPU.  Layers whose
+        # gradient accumulates over several launches (the RPN head over its five levels) keep the per-launch reduce, which orders them.
+        shared = ly.name.startswith("proposal_generator.")
+        T.conv_wgrad(x, dy, ly.dw, KH=ly.k, KW=ly.k, stride=ly.stride, pad=ly.pad, scale=ly.scale, accumulate=accumulate, precision=self.wgrad_prec,
+                     defer=self._defer if (BATCHED_LAUNCHES and not shared and not accumulate) else None)
+        if ly.db is not None:
+            T.colsum(dy, ly.db, accumulate=accumulate)
 
-    def _rpn_head_backward_early(self, names, dheads, t, feats, st):
-        """The RPN head's backward needs nothing but its loss gradient, which exists before the proposals are even selected -- and proposal
-        selection, NMS, matching, ROI sampling and the pooler are latency-bound launches of a few workgroups that leave the chip empty
-        (~1 ms of the 6 ms step at the reference's 2 images per GPU).  So (round 5) it is enqueued on a second stream right behind the RPN
-        loss and runs under that window.  Bits: each pyramid level's gradient is the sum of two terms (ROI pooler + RPN head); the serial
-        form adds the RPN term onto the pooler's (conv epilogue, residual), this form lets the pooler's backward add onto the RPN term --
-        a + b either way; p5's third term (from p6) is added last in both."""
-        main, R = self._cur_stream, self._rpn_stream
-        ev = self._next_event()
-        ev.record(main)
-        for ten in list(dheads) + list(t) + [feats[n] for n in names]:
-            ten.record_stream(R)
-        torch.cuda.set_stream(R)
-        self._cur_stream = R
-        try:
-            R.wait_event(ev)
-            out, dp6 = self._rpn_head_backward(names, dheads, t, feats, st)
-            done = self._next_event()
-            done.record(R)
-        finally:
-            torch.cuda.set_stream(main)
-            self._cur_stream = main
-        for ten in list(out.values()) + [dp6]:
-            ten.record_stream(main)
-        return out, dp6, done
+    def _segment_done(self, i: int):
+        """Every launch that writes gradient segment i (self.grad_segments) has been enqueued: fold the segment's parked slice reductions
+        and hand it to the gradient exchange.  All weight gradients of a step run in call order on ONE stream (the side stream, or the main
+        one), so 'behind the last of them on that stream' is behind all of them -- the hop needs no fork event.  Without a live exchange
+        (world 1, forward_backward called on its own) nothing happens here and the one flush at the end of the backward pass folds
+        everything, as before."""
+        if not self._xchg_live:
+            return
+        if self.grad_overlap.endswith("late"):
+            self._late.append(i)
+            return
+        hop(self, self._wg_stream, (), self._next_event, lambda: self._defer.flush(slot=1 + i), fork=False)
+        self._xchg.segment_ready(i, self._wg_stream if self._wg_stream is not None else self._cur_stream)
 
     def _gt_upload(self, gt_boxes, gt_classes, B):
         """Ground truth on the device: fixed-size [B, max_gt] tensors, counts in a device vector (nothing waits for the host)."""
@@ -463,78 +473,6 @@ class DetectorTrainer:
             gcount[i] = len(gb)
         return gtb.to(self.dev, non_blocking=True), gtc.to(self.dev, non_blocking=True), gcount.to(self.dev, non_blocking=True)
 
-    def _rpn_labels(self, anchors, gt_boxes, gt_classes, samples, seed, B):
-        """Ground truth on the device + the RPN's labels: Matcher + random sub-sampling (256 per image, <= half positive), both on the
-        device.  Depends on the ground truth and the anchor grid only."""
-        s = self.s
-        gtb_d, gtc_d, gcount_d = self._gt_upload(gt_boxes, gt_classes, B)
-        midx, lab = T.match_boxes(anchors, gtb_d, gcount_d, thresholds=s.rpn_iou_thresholds, labels=(0, -1, 1), allow_low_quality=True,
-                                  shared=True)
-        if samples is None:
-            labels_d = T.sample_labels(lab, num=s.rpn_batch_per_image, max_pos=int(s.rpn_batch_per_image * s.rpn_positive_fraction), seed=seed)
-        else:
-            labels_d = samples["anchor_labels"].to(torch.int8).to(self.dev)
-        return gtb_d, gtc_d, gcount_d, midx, lab, labels_d
-
-    def _rpn_labels_early(self, H, W, gt_boxes, gt_classes, samples, seed, B):
-        """The same on the second stream, enqueued before the backbone's forward pass: three small launches and the ground-truth upload leave
-        the step's dependent chain.  The pyramid's map sizes follow from the input size (every stride-2 stage: (h - 1) // 2 + 1)."""
-        f = lambda v: (v - 1) // 2 + 1
-        hw, (h, w) = [], (f(f(H)), f(f(W)))
-        for _ in self.strides:
-            hw.append((h, w))
-            h, w = f(h), f(w)
-        anchors = self._anchors(hw)
-        main, R = self._cur_stream, self._rpn_stream
-        ev = self._next_event()
-        ev.record(main)
-        torch.cuda.set_stream(R)
-        self._cur_stream = R
-        try:
-            R.wait_event(ev)
-            out = self._rpn_labels(anchors, gt_boxes, gt_classes, samples, seed, B)
-            ready = self._next_event()
-            ready.record(R)
-        finally:
-            torch.cuda.set_stream(main)
-            self._cur_stream = main
-        for ten in out:
-            ten.record_stream(main)
-        return hw, out + (ready,)
-
-    def _segment_done(self, i: int):
-        """Every launch that writes gradient segment i (self.grad_segments) has been enqueued: fold the segment's parked slice reductions
-        and hand it to the gradient exchange.  All weight gradients of a step run in call order on ONE stream (the side stream, or the main
-        one), so 'behind the last of them on that stream' is behind all of them.  Without a live exchange (world 1, forward_backward called
-        on its own) nothing happens here and the one flush at the end of the backward pass folds everything, as before."""
-        if not self._xchg_live:
-            return
-        if self.grad_overlap.endswith("late"):
-            self._late.append(i)
-            return
-        side, main = self._wg_stream, self._cur_stream
-        if side is not None:
-            torch.cuda.set_stream(side)
-        try:
-            if getattr(self, "_defer", None) is not None:
-                self._defer.flush(slot=1 + i)
-        finally:
-            if side is not None:
-                torch.cuda.set_stream(main)
-        self._xchg.segment_ready(i, side if side is not None else main)
-
-    def _wgrad_now(self, ly: _Layer, x, dy, accumulate=False):
-        # The slice reductions of the step's weight gradients are folded in ONE launch at the end of the backward pass (self._defer.flush()
-        # in forward_backward): 63 reduce launches of ~17 us each were 11 % of the step at the reference's 2 images per GPU.  Layers whose
-        # gradient accumulates over several launches (the RPN head over its five levels) keep the per-launch reduce, which orders them.
-        shared = ly.name.startswith("proposal_generator.")
-        if BATCHED_LAUNCHES and getattr(self, "_defer", None) is None:
-            self._defer = T.DeferredReduces(self.dev)
-        T.conv_wgrad(x, dy, ly.dw, KH=ly.k, KW=ly.k, stride=ly.stride, pad=ly.pad, scale=ly.scale, accumulate=accumulate, precision=self.wgrad_prec,
-                     defer=self._defer if (BATCHED_LAUNCHES and not shared and not accumulate) else None)
-        if ly.db is not None:
-            T.colsum(dy, ly.db, accumulate=accumulate)
-
     # ------------------------------------------------------------------------------------------ the step
     def forward_backward(self, frames_u8: torch.Tensor, gt_boxes: Sequence[torch.Tensor], gt_classes: Sequence[torch.Tensor],
                          samples: Optional[dict] = None, exchange: bool = False) -> Tuple[Dict[str, torch.Tensor], dict]:
@@ -542,22 +480,7 @@ class DetectorTrainer:
         Fills self.grads; returns ({loss name: 0-d device tensor}, aux with the sampled index sets).
         exchange=True (what `step` and the reference-style loop pass): the data-parallel gradient exchange starts INSIDE the backward pass,
         segment by segment (parallel.GradientExchange), and `optimizer_step` must follow -- until it has, self.grads is in flight."""
-        saved, ops.BF16_SPLITK_AUTO = ops.BF16_SPLITK_AUTO, True  # (split-K by batch size: the training step's launches only, ops.py)
-        self._cur_stream, self._wg_calls = torch.cuda.current_stream(), 0
-        if not hasattr(self, "_wg_events"):
-            self._wg_events = []
-        self._xchg_live, self._late = False, []
-        if exchange and self.grad_overlap != "0":
-            if self._xchg is None:
-                self._xchg = GradientExchange(self.grads, self.grad_segments, self.pg, self.grad_payload, force=self.grad_overlap.startswith("force"),
-                                              widen=False)
-            if self._xchg.active:
-                self._xchg.begin()
-                self._xchg_live = True
-        try:
-            return self._forward_backward(frames_u8, gt_boxes, gt_classes, samples)
-        finally:
-            ops.BF16_SPLITK_AUTO = saved
+        return self._run(self._train_step, exchange, frames_u8, gt_boxes, gt_classes, samples)
 
     def frozen_forward(self, frames_u8: torch.Tensor, gt_boxes: Sequence[torch.Tensor], gt_classes: Sequence[torch.Tensor],
                        samples: Optional[dict] = None) -> Tuple[Dict[str, torch.Tensor], dict]:
@@ -566,151 +489,206 @@ class DetectorTrainer:
         ROI sampling seed, so proposals, sampled index sets, classes and box losses are those `forward_backward` computes -- without the
         anchor labelling, the RPN loss, any kept activation or backward launch.  The parameters never change here, so the filters are
         prepared once.  -> ({loss_cls, loss_box_reg}, aux: pyramid, sampled ROIs, their matches, ground truth on the device)."""
+        return self._run(self._frozen_step, False, frames_u8, gt_boxes, gt_classes, samples)
+
+    def _run(self, body, exchange, *batch):
+        """body(*batch) as a step: split-K by batch size for the training step's launches only (ops.py)."""
         saved, ops.BF16_SPLITK_AUTO = ops.BF16_SPLITK_AUTO, True
-        self._cur_stream, self._wg_calls = torch.cuda.current_stream(), 0
-        if not hasattr(self, "_wg_events"):
-            self._wg_events = []
-        self._xchg_live, self._late = False, []
         try:
-            return self._forward_backward(frames_u8, gt_boxes, gt_classes, samples, frozen=True)
+            self._begin_step(exchange)
+            return body(*batch)
         finally:
             ops.BF16_SPLITK_AUTO = saved
 
-    def _forward_backward(self, frames_u8, gt_boxes, gt_classes, samples, frozen=False):
-        s, L, m = self.s, self.layers, self.model
+    def _begin_step(self, exchange: bool):
+        """The stream the step is enqueued on, its first reusable event, and the gradient exchange opened when asked for."""
+        self._cur_stream, self._wg_calls, self._late = torch.cuda.current_stream(), 0, []
+        self._xchg_live = open_exchange(self, exchange, widen=False)
+
+    def _train_step(self, frames_u8, gt_boxes, gt_classes, samples):
         B, H, W, _ = frames_u8.shape
-        # The per-step filter preparation (data-gradient transposes, bf16 copies: three HBM-bound launches over all parameters) does not touch
-        # the frozen stem / res2, so it runs on the side stream beside their forward pass; res3's first launch waits for it.
-        prepared = None
-        if frozen and getattr(self, "_frozen_prepared", False):
-            pass  # (frozen: the parameters have not changed since the last preparation)
-        elif self._wg_stream is not None:
-            main, side = self._cur_stream, self._wg_stream
-            ev = self._next_event()
-            ev.record(main)  # (behind the previous step's optimiser update)
-            torch.cuda.set_stream(side)
-            self._cur_stream = side
-            try:
-                side.wait_event(ev)
-                self._prepare_filters()
-                prepared = self._next_event()
-                prepared.record(side)
-            finally:
-                torch.cuda.set_stream(main)
-                self._cur_stream = main
-        else:
-            self._prepare_filters()
-        self._frozen_prepared = frozen
         seed = (self.seed * 1000003 + self.iter) * 4
-        labels_early, early_hw = None, None
-        if self._rpn_stream is not None and not frozen:  # ground-truth upload, anchor matching and label sampling: beside the backbone's forward pass
-            early_hw, labels_early = self._rpn_labels_early(H, W, gt_boxes, gt_classes, samples, seed, B)
-        saved = {}
-        relu_outputs = []  # every ReLU output on the trainable path, in forward order (aux: lets a checker reuse the gates)
+        prepared = self._filters_beside()
+        self._frozen_prepared = False  # (the optimiser step changes the parameters)
+        hw, labels, ready = self._labels_beside(H, W, gt_boxes, gt_classes, samples, seed, B)
+        blocks = []
+        res = self._trunk_forward(frames_u8, prepared, blocks)
+        prev, feats, t, heads = self._fpn_rpn_forward(res)
+        assert [tuple(feats[n].shape[1:3]) for n in LEVELS] == hw, hw
+        gtb_d, gtc_d, gcount_d, midx, lab, labels_d = labels
+        if ready is not None:  # (matched and sampled on the second stream while the backbone ran)
+            self._cur_stream.wait_event(ready)
+        rpn_l, dheads = T.rpn_loss(heads, self.strides, self.cell_anchors, labels_d, midx, gtb_d, A=3, weights=self.s.rpn_weights,
+                                   normalizer=float(self.s.rpn_batch_per_image * B))
+        early = self._rpn_head_backward_beside(dheads, t, feats)
+        rois = self._sample_rois(heads, (H, W), (gtb_d, gtc_d, gcount_d), samples, seed)
+        xrow, h1, h2, pred, box_l, dpred = self._box_forward(feats, rois)
+        dpooled = self._box_backward(xrow, h1, h2, dpred)
+        dprev = self._pyramid_backward(dpooled, rois, early, dheads, t, feats, prev, res)
+        self._res_backward(dprev, res, blocks)
+        self._finish_backward()
+        losses = {"loss_rpn_cls": rpn_l[0], "loss_rpn_loc": rpn_l[1], "loss_cls": box_l[0], "loss_box_reg": box_l[1]}
+        # (every ReLU output on the trainable path, in forward order: lets a checker reuse the gates)
+        relu_outputs = [o for _x, a, b, out in blocks for o in (a, b, out)] + list(t) + [h1.view(pred.shape[0], -1), h2.view(pred.shape[0], -1)]
+        aux = dict(relu_outputs=relu_outputs, anchor_labels=labels_d, roi_index=rois.index, roi_count=rois.count, roi_cls=rois.cls,
+                   proposals=rois.proposals, heads=heads, feats=feats, pred=pred, roi_boxes=rois.boxes, anchor_match=(midx, lab))
+        return losses, aux
+
+    def _frozen_step(self, frames_u8, gt_boxes, gt_classes, samples):
+        B, H, W, _ = frames_u8.shape
+        prepared = None if self._frozen_prepared else self._filters_beside()  # (the parameters have not changed since the last preparation)
+        self._frozen_prepared = True
+        res = self._trunk_forward(frames_u8, prepared)
+        _prev, feats, _t, heads = self._fpn_rpn_forward(res)
+        gt = self._gt_upload(gt_boxes, gt_classes, B)  # (no anchor labels: the RPN loss is dropped with the RPN frozen)
+        rois = self._sample_rois(heads, (H, W), gt, samples, (self.seed * 1000003 + self.iter) * 4)
+        pred, box_l = self._box_forward(feats, rois)[3:5]
+        return {"loss_cls": box_l[0], "loss_box_reg": box_l[1]}, dict(
+            feats=feats, proposals=rois.proposals, roi_boxes=rois.boxes, roi_cls=rois.cls, roi_index=rois.index, roi_count=rois.count,
+            proposal_match=rois.match, gt=gt, pred=pred)
+
+    # ---- the phases of the step, in the order a step runs them
+    def _filters_beside(self):
+        """The per-step filter preparation (data-gradient transposes, bf16 copies: three HBM-bound launches over all parameters) does not
+        touch the frozen stem / res2, so it runs on the side stream beside their forward pass, behind the previous step's optimiser update
+        -> the event res3's first launch waits for (None with one stream)."""
+        return hop(self, self._wg_stream, (), self._next_event, self._prepare_filters, done=True)[1]
+
+    def _labels_beside(self, H, W, gt_boxes, gt_classes, samples, seed, B):
+        """Ground truth on the device + the RPN's labels: Matcher + random sub-sampling (256 per image, <= half positive), both on the
+        device.  They depend on the ground truth and the anchor grid only, and the pyramid's map sizes follow from the input size (every
+        stride-2 stage: (h - 1) // 2 + 1), so they are enqueued on the second stream before the backbone's forward pass: three small
+        launches and the ground-truth upload leave the step's dependent chain.
+        -> (map sizes, (gt boxes, gt classes, gt counts, anchor matches, match labels, sampled labels), the event to wait for)."""
+        s, f = self.s, lambda v: (v - 1) // 2 + 1
+        hw, (h, w) = [], (f(f(H)), f(f(W)))
+        for _ in self.strides:
+            hw.append((h, w))
+            h, w = f(h), f(w)
+        anchors = self._anchors(hw)
+
+        def labels():
+            gtb_d, gtc_d, gcount_d = self._gt_upload(gt_boxes, gt_classes, B)
+            midx, lab = T.match_boxes(anchors, gtb_d, gcount_d, thresholds=s.rpn_iou_thresholds, labels=(0, -1, 1), allow_low_quality=True,
+                                      shared=True)
+            if samples is None:
+                labels_d = T.sample_labels(lab, num=s.rpn_batch_per_image, max_pos=int(s.rpn_batch_per_image * s.rpn_positive_fraction), seed=seed)
+            else:
+                labels_d = samples["anchor_labels"].to(torch.int8).to(self.dev)
+            return gtb_d, gtc_d, gcount_d, midx, lab, labels_d
+
+        out, ready = hop(self, self._rpn_stream, (), self._next_event, labels, done=True)
+        if ready is not None:
+            adopt(out, self._cur_stream)
+        return hw, out, ready
+
+    def _trunk_forward(self, frames_u8, prepared, blocks: Optional[list] = None):
+        """The frozen stem + res2 (FREEZE_AT 2: the inference launches), then res3..res5 behind `prepared` (their filters' event).
+        `blocks`: a training step's list, which takes every block's (input, conv1 out, conv2 out, output) -- the activations its backward
+        pass needs.  -> {res2..res5: stage output}."""
+        L, m, st = self.layers, self.model, self._st  # (bf16 storage: these four tensors per block are the step's big activations)
         with torch.no_grad():
             x4 = ops.preprocess_u8hwc(frames_u8.contiguous(), self.pixel_mean, self.pixel_std)
-            x = m.backbone.bottom_up.forward_stage("res2", m.backbone.bottom_up.stem(x4), frozen=True)  # frozen (FREEZE_AT 2): the inference launches
+            x = m.backbone.bottom_up.forward_stage("res2", m.backbone.bottom_up.stem(x4), frozen=True)
         res = {"res2": x}
         if prepared is not None:
             self._cur_stream.wait_event(prepared)
-        # ---- res3..res5 forward, activations kept
         for name, nblk, _mid, _cout in RES_STAGES:
             for i in range(nblk):
                 p = f"backbone.bottom_up.{name}.{i}."
-                st = self._st  # (bf16 storage: these four tensors per block are the step's big activations)
                 sc = self._conv(x, L[p + "shortcut"].fwd(), out_dtype=st) if i == 0 else x
                 a = self._conv(x, L[p + "conv1"].fwd(), out_dtype=st)
                 b = self._conv(a, L[p + "conv2"].fwd(), out_dtype=st)
                 out = self._conv(b, L[p + "conv3"].fwd(), res=sc, out_dtype=st)
-                if not frozen:
-                    saved[p] = (x, a, b)
-                    relu_outputs += [a, b, out]
+                if blocks is not None:
+                    blocks.append((x, a, b, out))
                 x = out
             res[name] = x
-        # ---- FPN
-        prev, feats = {}, {}
-        # (bf16 storage, round 4: the lateral sums, the RPN hidden maps, the box head's hidden rows and the gradients flowing back through
-        # them are stored as bf16 too -- what torch.autocast keeps of them; the pyramid p2..p6 itself stays fp32: the pooler and the proposal
-        # decoder read it, and its gradient is accumulated from two branches)
-        st = self._st
-        names = ("p2", "p3", "p4", "p5", "p6")
-        rp = "proposal_generator.rpn_head."
-        tmap, hmap = {}, {}
+        return res
 
-        def level_heads(n):  # the RPN head on one pyramid level (shared filters; the levels are independent of each other)
+    def _fpn_rpn_forward(self, res):
+        """The FPN and the RPN head on every level -> (lateral sums {level: map}, pyramid {p2..p6}, the RPN's hidden maps, its predictions;
+        the last two as lists in LEVELS order).  The top-down lateral chain (four small launches) and the finest level stay on the main
+        stream; the output convs and RPN heads of p3..p6 run on the second stream beside p2's (same launches, same bits).
+        (bf16 storage, round 4: the lateral sums, the RPN hidden maps, the box head's hidden rows and the gradients flowing back through
+        them are stored as bf16 too -- what torch.autocast keeps of them; the pyramid p2..p6 itself stays fp32: the pooler and the proposal
+        decoder read it, and its gradient is accumulated from two branches)"""
+        L, st, rp = self.layers, self._st, "proposal_generator.rpn_head."
+        prev, feats, tmap, hmap = {}, {}, {}, {}
+
+        def rpn_head(n):  # the RPN head on one pyramid level (shared filters; the levels are independent of each other)
             tmap[n] = self._conv(feats[n], L[rp + "conv"].fwd(), out_dtype=st)
             hmap[n] = self._conv(tmap[n], L[rp + "pred"].fwd())
 
-        R = self._rpn_stream
-        if R is None:
-            prev[5] = self._conv(res["res5"], L["backbone.fpn_lateral5"].fwd(), out_dtype=st)
-            feats["p5"] = self._conv(prev[5], L["backbone.fpn_output5"].fwd())
-            for l in (4, 3, 2):
-                prev[l] = self._conv(res[f"res{l}"], L[f"backbone.fpn_lateral{l}"].fwd(), res=prev[l + 1], res_ups=True, out_dtype=st)
-                feats[f"p{l}"] = self._conv(prev[l], L[f"backbone.fpn_output{l}"].fwd())
-            feats["p6"] = ops.subsample2(feats["p5"])
-            for n in names:
-                level_heads(n)
-        else:
-            # The top-down lateral chain (four small launches) and the finest level stay on the main stream; the output convs and RPN heads of
-            # p3..p6 -- each waiting for its own lateral sum only -- run on the second stream beside them (same launches, same bits).
-            main = self._cur_stream
-            lat_done = {}
-            prev[5] = self._conv(res["res5"], L["backbone.fpn_lateral5"].fwd(), out_dtype=st)
-            lat_done[5] = self._next_event()
-            lat_done[5].record(main)
-            for l in (4, 3, 2):
-                prev[l] = self._conv(res[f"res{l}"], L[f"backbone.fpn_lateral{l}"].fwd(), res=prev[l + 1], res_ups=True, out_dtype=st)
-                if l > 2:
-                    lat_done[l] = self._next_event()
-                    lat_done[l].record(main)
-            for l in (5, 4, 3):
-                prev[l].record_stream(R)
-            torch.cuda.set_stream(R)
-            self._cur_stream = R
-            try:
-                for l in (5, 4, 3):
-                    R.wait_event(lat_done[l])
-                    feats[f"p{l}"] = self._conv(prev[l], L[f"backbone.fpn_output{l}"].fwd())
-                    level_heads(f"p{l}")
-                    if l == 5:
-                        feats["p6"] = ops.subsample2(feats["p5"])
-                        level_heads("p6")
-                coarse_done = self._next_event()
-                coarse_done.record(R)
-            finally:
-                torch.cuda.set_stream(main)
-                self._cur_stream = main
-            feats["p2"] = self._conv(prev[2], L["backbone.fpn_output2"].fwd())
-            level_heads("p2")
-            main.wait_event(coarse_done)
-            for n in ("p3", "p4", "p5", "p6"):
-                for ten in (feats[n], tmap[n], hmap[n]):
-                    ten.record_stream(main)
-        t = [tmap[n] for n in names]
-        heads = [hmap[n] for n in names]
-        feat_hw = [tuple(feats[n].shape[1:3]) for n in names]
-        anchors = self._anchors(feat_hw)
-        if frozen:  # (no anchor labels: the RPN loss is dropped with the RPN frozen)
-            gtb_d, gtc_d, gcount_d = self._gt_upload(gt_boxes, gt_classes, B)
-        elif labels_early is None:
-            gtb_d, gtc_d, gcount_d, midx, lab, labels_d = self._rpn_labels(anchors, gt_boxes, gt_classes, samples, seed, B)
-        else:  # (matched and sampled on the second stream while the backbone ran)
-            assert tuple(feat_hw) == tuple(early_hw), (feat_hw, early_hw)
-            gtb_d, gtc_d, gcount_d, midx, lab, labels_d, ready = labels_early
-            self._cur_stream.wait_event(ready)
-        if not frozen:
-            rpn_l, dheads = T.rpn_loss(heads, self.strides, self.cell_anchors, labels_d, midx, gtb_d, A=3, weights=s.rpn_weights,
-                                       normalizer=float(s.rpn_batch_per_image * B))
-            early = self._rpn_head_backward_early(names, dheads, t, feats, st) if self._rpn_stream is not None else None
-        # ---- proposals (no gradient) + ground truth, Matcher, sub-sampling (512 per image, <= a quarter foreground)
-        pb, _ps, _lvl, _pos, pcount = ops.rpn_proposals(heads, self.strides, self.cell_anchors, (H, W), pre_topk=s.rpn_pre_topk_train,
+        def level(l):
+            if l in lat_done:  # (on the second stream: each level waits for its own lateral sum only)
+                self._cur_stream.wait_event(lat_done[l])
+            feats[f"p{l}"] = self._conv(prev[l], L[f"backbone.fpn_output{l}"].fwd())
+            rpn_head(f"p{l}")
+            if l == 5:
+                feats["p6"] = ops.subsample2(feats["p5"])
+                rpn_head("p6")
+
+        lat_done = {}
+        for l in (5, 4, 3, 2):
+            top = {} if l == 5 else dict(res=prev[l + 1], res_ups=True)
+            prev[l] = self._conv(res[f"res{l}"], L[f"backbone.fpn_lateral{l}"].fwd(), out_dtype=st, **top)
+            if l > 2 and self._rpn_stream is not None:
+                lat_done[l] = self._next_event()
+                lat_done[l].record(self._cur_stream)
+        _, coarse_done = hop(self, self._rpn_stream, (prev[5], prev[4], prev[3]), self._next_event,
+                             lambda: [level(l) for l in (5, 4, 3)], done=True, fork=False)
+        level(2)
+        if coarse_done is not None:
+            self._cur_stream.wait_event(coarse_done)
+            adopt([m[n] for n in LEVELS[1:] for m in (feats, tmap, hmap)], self._cur_stream)
+        return prev, feats, [tmap[n] for n in LEVELS], [hmap[n] for n in LEVELS]
+
+    def _rpn_head_backward_beside(self, dheads, t, feats):
+        """The RPN head's backward needs nothing but its loss gradient, which exists before the proposals are even selected -- and proposal
+        selection, NMS, matching, ROI sampling and the pooler are latency-bound launches of a few workgroups that leave the chip empty
+        (~1 ms of the 6 ms step at the reference's 2 images per GPU).  So (round 5) it is enqueued on a second stream right behind the RPN
+        loss and runs under that window.  Bits: each pyramid level's gradient is the sum of two terms (ROI pooler + RPN head); the serial
+        form adds the RPN term onto the pooler's (conv epilogue, residual), this form lets the pooler's backward add onto the RPN term --
+        a + b either way; p5's third term (from p6) is added last in both.
+        -> ({level: gradient}, p6's gradient, the event to wait for), or None with one stream: the serial form runs in its place."""
+        if self._rpn_stream is None:
+            return None
+        (out, dp6), done = hop(self, self._rpn_stream, list(dheads) + list(t) + [feats[n] for n in LEVELS], self._next_event,
+                               lambda: self._rpn_head_backward(dheads, t, feats), done=True)
+        adopt(list(out.values()) + [dp6], self._cur_stream)
+        return out, dp6, done
+
+    def _rpn_head_backward(self, dheads, t, feats, dP=None):
+        """Data and weight gradients of the RPN head (filters shared by the five levels: weight gradients accumulate in level order).
+        dP given: the serial form -- every level's gradient is added to dP[level] (p6's to p5 through the stride-2 subsample) and None is
+        returned.  dP None: the early form -- returns ({level: gradient}, dp6) for the caller to combine."""
+        L, rp = self.layers, "proposal_generator.rpn_head."
+        out, dp6 = {}, None
+        for li, n in enumerate(LEVELS):
+            dt = self._conv(dheads[li], L[rp + "pred"].bwd(), gate=t[li], out_dtype=self._st)
+            self._wgrad(L[rp + "pred"], t[li], dheads[li], accumulate=li > 0)
+            self._wgrad(L[rp + "conv"], feats[n], dt, accumulate=li > 0)
+            if n == "p6":
+                dp6 = self._conv(dt, L[rp + "conv"].bwd(), wino=False)
+                if dP is not None:
+                    T.zero_insert2(dp6, dP["p5"].shape[1], dP["p5"].shape[2], out=dP["p5"], accumulate=True)
+            elif dP is not None:
+                self._conv(dt, L[rp + "conv"].bwd(), res=dP[n], out=dP[n], wino=False)
+            else:
+                out[n] = self._conv(dt, L[rp + "conv"].bwd(), wino=False)
+        return None if dP is not None else (out, dp6)
+
+    def _sample_rois(self, heads, image_hw, gt, samples, seed) -> _Rois:
+        """Proposals (no gradient) + ground truth, Matcher, sub-sampling (512 per image, <= a quarter foreground)."""
+        s, (gtb_d, gtc_d, gcount_d) = self.s, gt
+        pb, _ps, _lvl, _pos, pcount = ops.rpn_proposals(heads, self.strides, self.cell_anchors, image_hw, pre_topk=s.rpn_pre_topk_train,
                                                         post_topk=s.rpn_post_topk_train, nms_thresh=s.rpn_nms_thresh, min_size=0.0,
                                                         weights=s.rpn_weights, scale_clamp=math.log(1000.0 / 16))
         allb, bcount = T.append_gt_boxes(pb, pcount, gtb_d, gcount_d)
         pmidx, plab = T.match_boxes(allb, gtb_d, gcount_d, thresholds=(s.roi_iou_threshold,), labels=(0, 1), allow_low_quality=False,
                                     box_count=bcount)
-        Rs = s.roi_batch_per_image
+        B, Rs = gtb_d.shape[0], s.roi_batch_per_image
         if samples is None:
             roi_boxes, roi_gt, roi_cls, roi_index, rcount_d = T.sample_rois(
                 allb, bcount, gtb_d, gtc_d, gcount_d, pmidx, plab, num_classes=s.num_classes, num=Rs,
@@ -729,63 +707,68 @@ class DetectorTrainer:
             roi_gt = (torch.gather(gtb_d, 1, msel[:, :, None].expand(B, Rs, 4)) * live[:, :, None]).contiguous()
             fg = (torch.gather(plab.long(), 1, sel) == 1) & (gcount_d[:, None] > 0)
             roi_cls = torch.where(fg & live, torch.gather(gtc_d.long(), 1, msel), torch.full_like(msel, s.num_classes)).to(torch.int32).contiguous()
-        M = B * Rs  # fixed row count: slots past rcount[b] are zero rows that carry neither loss nor gradient
-        # ---- box head forward
-        pyr = [feats[n] for n in ("p2", "p3", "p4", "p5")]
-        scales = [1.0 / FPN_STRIDES[n] for n in ("p2", "p3", "p4", "p5")]
-        pooled = ops.roi_align_fpn(pyr, scales, roi_boxes, rcount_d, 7, 0, True, zero=True)
-        bh, bp = "roi_heads.box_head.", "roi_heads.box_predictor."
+        return _Rois(roi_boxes, roi_gt, roi_cls, roi_index, rcount_d, (pb, pcount), pmidx)
+
+    def _box_forward(self, feats, rois: _Rois):
+        """The box head over the pooled ROIs and its loss -> (pooled rows, fc1 out, fc2 out, predictions [M, 32], (loss_cls, loss_box_reg),
+        the loss's gradient).  M = B x roi_batch_per_image, a fixed row count: slots past rois.count[b] are zero rows that carry neither
+        loss nor gradient."""
+        L, s, st, bh = self.layers, self.s, self._st, "roi_heads.box_head."
+        M = rois.boxes.shape[0] * rois.boxes.shape[1]
+        pooled = ops.roi_align_fpn([feats[n] for n in LEVELS[:4]], ROI_SCALES, rois.boxes, rois.count, 7, 0, True, zero=True)
         xrow = pooled.view(M, 1, 1, 49 * 256)
         h1 = self._conv(xrow, L[bh + "fc1"].fwd(), out_dtype=st)
         h2 = self._conv(h1, L[bh + "fc2"].fwd(), out_dtype=st)
-        pred = self._conv(h2, L[bp + "pred"].fwd())
-        box_l, dpred = T.box_loss(pred.view(M, 32), roi_cls.view(M), roi_boxes.view(M, 4), roi_gt.view(M, 4), num_classes=s.num_classes,
-                                  weights=s.box_weights, count=rcount_d, rows_per_image=Rs)
-        if frozen:
-            return {"loss_cls": box_l[0], "loss_box_reg": box_l[1]}, dict(
-                feats=feats, proposals=(pb, pcount), roi_boxes=roi_boxes, roi_cls=roi_cls, roi_index=roi_index, roi_count=rcount_d,
-                proposal_match=pmidx, gt=(gtb_d, gtc_d, gcount_d), pred=pred.view(M, 32))
-        losses = {"loss_rpn_cls": rpn_l[0], "loss_rpn_loc": rpn_l[1], "loss_cls": box_l[0], "loss_box_reg": box_l[1]}
+        pred = self._conv(h2, L["roi_heads.box_predictor.pred"].fwd()).view(M, 32)
+        box_l, dpred = T.box_loss(pred, rois.cls.view(M), rois.boxes.view(M, 4), rois.gt.view(M, 4), num_classes=s.num_classes,
+                                  weights=s.box_weights, count=rois.count, rows_per_image=s.roi_batch_per_image)
+        return xrow, h1, h2, pred, box_l, dpred
 
-        # ======================================== backward ========================================
-        dpred = dpred.view(M, 1, 1, 32)
+    def _box_backward(self, xrow, h1, h2, dpred):
+        """-> the gradient of the pooled rows [M,1,1,12544]."""
+        L, st, bh, bp = self.layers, self._st, "roi_heads.box_head.", "roi_heads.box_predictor."
+        dpred = dpred.view(-1, 1, 1, 32)
         self._wgrad(L[bp + "pred"], h2, dpred)
         dh2 = self._conv(dpred, L[bp + "pred"].bwd(), gate=h2, out_dtype=st)
         self._wgrad(L[bh + "fc2"], h1, dh2)
         dh1 = self._conv(dh2, L[bh + "fc2"].bwd(), gate=h1, out_dtype=st)
         self._wgrad(L[bh + "fc1"], xrow, dh1)
         self._segment_done(0)  # box head + predictor: 13.9 M of the 41 M gradients leave at the very start of the backward pass
-        dpooled = self._conv(dh1, L[bh + "fc1"].bwd())  # [M,1,1,12544]
-        if early is not None:  # the RPN head's term of every level is there already (second stream): the pooler's backward adds onto it
+        return self._conv(dh1, L[bh + "fc1"].bwd())
+
+    def _pyramid_backward(self, dpooled, rois: _Rois, early, dheads, t, feats, prev, res):
+        """The pooler's and the RPN head's backward into the pyramid, then the FPN's -> {level: gradient of the lateral sum}."""
+        L, fine = self.layers, LEVELS[:4]
+        if early is None:
+            dP = {n: torch.zeros_like(feats[n]) for n in fine}
+        else:  # the RPN head's term of every level is there already (second stream): the pooler's backward adds onto it
             dP, dp6, done = early
             self._cur_stream.wait_event(done)
-            T.roi_align_fpn_backward([dP[n] for n in ("p2", "p3", "p4", "p5")], scales, roi_boxes, dpooled.view(M, 7, 7, 256), P=7,
-                                     sampling_ratio=0, aligned=True, count=rcount_d)
-            T.zero_insert2(dp6, dP["p5"].shape[1], dP["p5"].shape[2], out=dP["p5"], accumulate=True)
+        T.roi_align_fpn_backward([dP[n] for n in fine], ROI_SCALES, rois.boxes, dpooled.view(-1, 7, 7, 256), P=7, sampling_ratio=0, aligned=True,
+                                 count=rois.count)
+        if early is None:  # (weights shared by the five levels: gradients accumulate in level order)
+            self._rpn_head_backward(dheads, t, feats, dP=dP)
         else:
-            dP = {n: torch.zeros_like(feats[n]) for n in ("p2", "p3", "p4", "p5")}
-            T.roi_align_fpn_backward([dP[n] for n in ("p2", "p3", "p4", "p5")], scales, roi_boxes, dpooled.view(M, 7, 7, 256), P=7,
-                                     sampling_ratio=0, aligned=True, count=rcount_d)
-            # ---- RPN head backward (weights shared by the five levels: gradients accumulate in level order)
-            self._rpn_head_backward(names, dheads, t, feats, st, dP=dP)
-        # ---- FPN backward (finest level first: the top-down path carries gradient upwards)
+            T.zero_insert2(dp6, dP["p5"].shape[1], dP["p5"].shape[2], out=dP["p5"], accumulate=True)
         dprev = {}
-        for l in (2, 3, 4, 5):
+        for l in (2, 3, 4, 5):  # finest level first: the top-down path carries gradient upwards
             lo = L[f"backbone.fpn_output{l}"]
             self._wgrad(lo, prev[l], dP[f"p{l}"])
             dprev[l] = self._conv(dP[f"p{l}"], lo.bwd())
             if l > 2:
                 T.sumpool2_add(dprev[l - 1], dprev[l])
             self._wgrad(L[f"backbone.fpn_lateral{l}"], res[f"res{l}"], dprev[l])
-        # ---- ResNet backward
+        return dprev
+
+    def _res_backward(self, dprev, res, blocks):
+        L, st, blocks = self.layers, self._st, iter(reversed(blocks))
         dx_up = None  # gradient arriving at a stage output from the stage above (un-gated)
         for name, nblk, _mid, _cout in reversed(RES_STAGES):
             l = int(name[3:])
-            st = self._st
             g = self._conv(dprev[l], L[f"backbone.fpn_lateral{l}"].bwd(), res=dx_up, gate=res[name], out_dtype=st)
             for i in reversed(range(nblk)):
                 p = f"backbone.bottom_up.{name}.{i}."
-                x_in, a, b = saved[p]
+                x_in, a, b, _out = next(blocks)
                 c1, c2, c3 = L[p + "conv1"], L[p + "conv2"], L[p + "conv3"]
                 self._wgrad(c3, b, g)
                 db_ = self._conv(g, c3.bwd(), gate=b, out_dtype=st)
@@ -802,20 +785,17 @@ class DetectorTrainer:
                 else:
                     g = self._conv(da_, c1.bwd(), res=g, gate=x_in, out_dtype=st)
             self._segment_done({"res5": 1, "res4": 2, "res3": 3}[name])  # (res5's segment carries the FPN and the RPN head, finished before it)
+
+    def _finish_backward(self):
         if self._wg_stream is not None:
             self._cur_stream.wait_stream(self._wg_stream)  # every weight gradient has been launched and is waited for here
-        if getattr(self, "_defer", None) is not None:
-            # every parked weight gradient: one reduce launch.  (Flushed in pieces on the side stream, under the rest of the backward pass:
-            # measured slower the finer the pieces -- 352 | 347 | 342 | 338 images/s at 2 images per GPU for one | 24 | 12 | 6 layers per
-            # flush: the reduce is HBM-bound and takes its bandwidth from the chain it runs beside.)
-            self._defer.flush()
+        # every parked weight gradient: one reduce launch.  (Flushed in pieces on the side stream, under the rest of the backward pass:
+        # measured slower the finer the pieces -- 352 | 347 | 342 | 338 images/s at 2 images per GPU for one | 24 | 12 | 6 layers per
+        # flush: the reduce is HBM-bound and takes its bandwidth from the chain it runs beside.)
+        self._defer.flush()
         for i in self._late:  # ("late" forms: every segment behind the whole backward pass, on the main stream)
             self._xchg.segment_ready(i, self._cur_stream)
         self._late = []
-        relu_outputs += list(t) + [h1.view(M, -1), h2.view(M, -1)]
-        aux = dict(relu_outputs=relu_outputs, anchor_labels=labels_d, roi_index=roi_index, roi_count=rcount_d, roi_cls=roi_cls,
-                   proposals=(pb, pcount), heads=heads, feats=feats, pred=pred.view(M, 32), roi_boxes=roi_boxes, anchor_match=(midx, lab))
-        return losses, aux
 
     @staticmethod
     def batch_extras(batched_inputs) -> tuple:
@@ -824,8 +804,6 @@ class DetectorTrainer:
 
     def autograd_anchor(self) -> torch.Tensor:
         """A leaf that requires grad, so that the loss scalars handed out by PlaneRCNN.training_forward can be `.backward()`-ed."""
-        if getattr(self, "_anchor", None) is None:
-            self._anchor = torch.zeros((), device=self.dev, requires_grad=True)
         return self._anchor
 
     def optimizer_step(self):

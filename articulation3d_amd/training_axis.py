@@ -31,6 +31,7 @@ import torch
 
 from . import ops, train_ops as T
 from .ops import ACT_NONE, ACT_RELU
+from .streams import adopt, hop, side as side_stream
 from .training import SolverCfg, _Layer
 from .training_head import HeadTrainer, fc_columns_to_chw, fc_columns_to_hwc
 
@@ -70,9 +71,7 @@ class AxisTrainer(HeadTrainer):
         self.beta = float(ah.smooth_l1_beta if beta is None else beta)
         self.loss_weight = float(ah._loss_weight if loss_weight is None else loss_weight)
         super().__init__(model, solver, seed, process_group, precision, grad_payload, storage, grad_overlap)
-        from .streams import side
-
-        self._t_stream = side(1, self.dev) if AXIS_TOWER_STREAM else None
+        self._t_stream = side_stream(1, self.dev) if AXIS_TOWER_STREAM else None
 
     _layer_table = staticmethod(axis_layer_table)
 
@@ -126,32 +125,22 @@ class AxisTrainer(HeadTrainer):
         dx = self._conv(dh, fc.bwd(), live, gate=xf).view(M, P14, P14, 256)
         self._tower_backward(CONVS[t], acts, dx, live_px)
 
-    def _beside(self, main, tensors, fn):
-        """fn() on the T tower's stream, behind what the main stream holds now (`tensors`: what fn reads of the main stream's)."""
-        side = self._t_stream
-        ev = torch.cuda.Event()
-        ev.record(main)
-        for ten in tensors:
-            ten.record_stream(side)
-        torch.cuda.set_stream(side)
-        try:
-            side.wait_event(ev)
-            return fn()
-        finally:
-            torch.cuda.set_stream(main)
+    def _beside(self, tensors, fn):
+        """fn() on the T tower's stream, behind what the main stream holds now (`tensors`: what fn reads of the main stream's).  The
+        frozen detector's step has ended on the main stream: its stream cursor and reusable events carry on into the head."""
+        return hop(self.det, self._t_stream, tensors, self.det._next_event, fn)
 
     def _head(self, losses, aux, fgd, live, live_px, pooled, gt):
         main, side = torch.cuda.current_stream(), self._t_stream
         # ---- tower R on the current stream, tower T beside it
         if side is not None:
-            t_out = self._beside(main, (pooled, live, live_px), lambda: self._axis_forward("T", pooled, live, live_px))
+            t_out = self._beside((pooled, live, live_px), lambda: self._axis_forward("T", pooled, live, live_px))
         r_out = self._axis_forward("R", pooled, live, live_px)
         if side is None:
             t_out = self._axis_forward("T", pooled, live, live_px)
         else:
             main.wait_stream(side)
-            for ten in t_out[0] + [t_out[1], t_out[2], t_out[3]]:
-                ten.record_stream(main)
+            adopt(t_out[0] + [t_out[1], t_out[2], t_out[3]], main)
         axl, d_rot, d_tran = T.axis_loss(r_out[3], t_out[3], live, fgd["row_img"], fgd["row_gt"], *gt, beta=self.beta,
                                          loss_weight=self.loss_weight)
         self._mark("axis_forward")
@@ -163,7 +152,7 @@ class AxisTrainer(HeadTrainer):
             self._segment_ready(1, stream)
 
         if side is not None:
-            self._beside(main, (d_tran,), lambda: t_backward(side))
+            self._beside((d_tran,), lambda: t_backward(side))
         self._axis_backward("R", *r_out[:3], d_rot, live, live_px)
         self._segment_ready(0, main)
         if side is None:

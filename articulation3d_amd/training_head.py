@@ -16,41 +16,13 @@ head's forward pass, loss and backward pass.
 """
 from __future__ import annotations
 
-from typing import Dict, NamedTuple, Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
 from . import ops, train_ops as T
 from .parallel import GradientExchange, allreduce_gradients
-from .training import DetectorTrainer, SolverCfg, _Layer, lr_at
-
-
-class FlatLayout(NamedTuple):
-    layers: Dict[str, Tuple[int, int, int, int]]  # name -> (weight offset, weights, bias offset, biases)
-    tail: Dict[str, Tuple[int, int]]  # name -> (offset, length): what follows the layers
-    total: int  # padded to a multiple of 4
-    segments: list  # [(begin, end)]: the gradient-exchange segments
-
-
-def flat_layout(layers: Sequence[_Layer], bias_rows: Optional[Dict[str, int]] = None, tail: Sequence[Tuple[str, int]] = (),
-                cuts: Sequence[str] = ()) -> FlatLayout:
-    """Where everything lies in the flat buffers: per layer its weights then its biases, in table order, then the tail entries.  A layer
-    has `rows` biases unless `bias_rows` names another count; a new gradient-exchange segment begins at every layer named in `cuts`.
-    Allocates nothing."""
-    out, ends, off = {}, [0], 0
-    for ly in layers:
-        if ly.name in cuts:
-            assert off % 4 == 0
-            ends.append(off)
-        nw, nb = ly.rows * ly.k * ly.k * ly.cin, (bias_rows or {}).get(ly.name, ly.rows)
-        out[ly.name] = (off, nw, off + nw, nb)
-        off += nw + nb
-    tails = {}
-    for name, n in tail:
-        tails[name] = (off, n)
-        off += n
-    ends.append((off + 3) // 4 * 4)
-    return FlatLayout(out, tails, ends[-1], list(zip(ends[:-1], ends[1:])))
+from .training import DetectorTrainer, FlatLayout, SolverCfg, _Layer, flat_layout, lr_at, open_exchange  # noqa: F401 (FlatLayout: importable from here)
 
 
 def fc_columns_to_hwc(w: torch.Tensor, channels: int, size: int) -> torch.Tensor:
@@ -246,24 +218,13 @@ class HeadTrainer:
         """The `start` mark and the frozen detector's forward pass of a step (the ground truth has been checked and uploaded)."""
         self._mark("start")
         self._grad_scale = 1.0  # (self.grads is this rank's own gradient until optimizer_step has exchanged it)
-        saved_sk, ops.BF16_SPLITK_AUTO = ops.BF16_SPLITK_AUTO, True
-        try:
-            self.det.iter = self.iter  # (the ROI sampling seed follows the step count, as in stage 1)
-            return self.det.frozen_forward(frames_u8, gt_boxes, gt_classes, samples)
-        finally:
-            ops.BF16_SPLITK_AUTO = saved_sk
+        self.det.iter = self.iter  # (the ROI sampling seed follows the step count, as in stage 1)
+        return self.det.frozen_forward(frames_u8, gt_boxes, gt_classes, samples)
 
     def _begin_head(self, exchange: bool):
         """In front of the head's launches: the gradient exchange opens (exchange=True) and the data-gradient filters of the current
         weights are made."""
-        self._xchg_live = False
-        if exchange and self.grad_overlap != "0":
-            if self._xchg is None:
-                self._xchg = GradientExchange(self.grads, self.grad_segments, self.pg, self.grad_payload,
-                                              force=self.grad_overlap.startswith("force"))
-            if self._xchg.active:
-                self._xchg.begin()
-                self._xchg_live = True
+        self._xchg_live = open_exchange(self, exchange)
         if self._tbatch is None:
             self._tbatch = T.TransposeBatch([(ly.w, None, ly.wt, ly.rows, ly.k, ly.k, ly.cin) for ly in self.layers.values()], self.dev)
         self._tbatch.run()
