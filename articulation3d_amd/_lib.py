@@ -288,6 +288,17 @@ class MeshDesc(C.Structure):
 
 
 JPEG_BLOCK_BITS, JPEG_HUFF_VALS = 1658, 162
+JPEG_RANGE, JPEG_BAD_CODE, JPEG_SHORT, JPEG_TABSET_BYTES = 1, 2, 3, 192 + 6 * (16 + 256)
+
+
+class JpegDecodeDesc(C.Structure):
+    _fields_ = [
+        ("F", C.c_int), ("H", C.c_int), ("W", C.c_int), ("pitch", C.c_int), ("ncomp", C.c_int), ("hs", C.c_int), ("vs", C.c_int),
+        ("n_units", C.c_int), ("n_sets", C.c_int), ("data_bytes", C.c_longlong),
+        ("unit_off", C.POINTER(C.c_int)), ("frame_unit", C.POINTER(C.c_int)), ("frame_ri", C.POINTER(C.c_int)), ("frame_set", C.POINTER(C.c_int)),
+        ("sets", C.POINTER(C.c_ubyte)),
+        ("d_data", fptr), ("d_meta", fptr), ("d_sets", fptr), ("coef", fptr), ("planes", fptr), ("rgb", fptr), ("status", fptr),
+    ]
 EVAL_DET_COLS, EVAL_GT_FCOLS, EVAL_GT_ICOLS, EVAL_MAX_GT, EVAL_MAX_CLASSES = 14, 7, 12, 64, 64
 
 
@@ -434,6 +445,8 @@ SIGNATURES = {
     "a3d_jpeg_slot_bytes": (C.c_size_t, [C.c_int]),
     "a3d_jpeg_encode": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr]),
     "a3d_jpeg_pack": (C.c_int, [fptr, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, C.c_longlong, fptr]),
+    "a3d_jpeg_decode_scratch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "a3d_jpeg_decode": (C.c_int, [C.POINTER(JpegDecodeDesc), fptr]),
     "a3d_sgd_momentum": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_sgd_momentum_bf16g": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_f32_to_bf16_scaled": (C.c_int, [fptr, fptr, C.c_size_t, C.c_float, fptr]),
@@ -444,7 +457,7 @@ STRUCT_IDS = {0: ConvDesc, 1: RpnDesc, 2: BoxDetDesc, 3: RoiAlignDesc, 4: PasteD
               7: RoiAlignBwdDesc, 8: MatchDesc, 9: RpnLossDesc, 10: BoxLossDesc, 11: RoiSampleDesc, 12: SweepDesc, 13: TransposeItem,
               14: AxisLossDesc, 15: MaskTargetsDesc, 16: MaskLossDesc, 17: PlaneLossDesc, 18: BnTrainDesc, 19: DepthLossDesc, 20: PredBwdDesc,
               21: RenderLayer, 22: RenderPiece, 23: RenderDesc, 24: MeshDesc, 25: EvalMatchDesc, 26: EvalApDesc, 27: DepthL1Desc,
-              28: EvalMaskCountsDesc, 29: EvalPlaneMatchDesc}
+              28: EvalMaskCountsDesc, 29: EvalPlaneMatchDesc, 30: JpegDecodeDesc}
 
 _lib = None
 

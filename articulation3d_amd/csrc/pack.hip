@@ -196,6 +196,7 @@ extern "C" size_t a3d_struct_size(int id) {
         case 27: return sizeof(a3d_depth_l1_desc);
         case 28: return sizeof(a3d_eval_mask_counts_desc);
         case 29: return sizeof(a3d_eval_plane_match_desc);
+        case 30: return sizeof(a3d_jpeg_decode_desc);
         default: return 0;
     }
 }

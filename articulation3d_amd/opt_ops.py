@@ -306,3 +306,37 @@ def jpeg_pack_into(slots: torch.Tensor, seg_off: torch.Tensor, seg_len: torch.Te
         raise ValueError("a buffer of a3d_jpeg_pack is smaller than the call needs")
     _lib.check(_lib.lib().a3d_jpeg_pack(_p(slots), _p(seg_off), _p(seg_len), int(F_), H, W, _p(_req(packed, torch.uint8)), packed.numel(), _stream()),
                "a3d_jpeg_pack")
+
+
+def jpeg_decode_scratch(H: int, W: int, ncomp: int, hs: int, vs: int):
+    """(int16 coefficient elements, uint8 plane elements) that a3d_jpeg_decode needs PER FRAME of this geometry."""
+    coef, planes = C.c_size_t(), C.c_size_t()
+    if _lib.lib().a3d_jpeg_decode_scratch(int(H), int(W), int(ncomp), int(hs), int(vs), C.byref(coef), C.byref(planes)) != 0:
+        raise ValueError(f"{H} x {W}, {ncomp} component(s), luma {hs}x{vs}: outside the decoder's law")
+    return int(coef.value), int(planes.value)
+
+
+def jpeg_decode_into(rgb: torch.Tensor, status: torch.Tensor, data: torch.Tensor, data_bytes: int, meta, meta_dev: torch.Tensor, sets,
+                     sets_dev: torch.Tensor, n_units: int, ncomp: int, hs: int, vs: int, coef: torch.Tensor, planes: torch.Tensor) -> None:
+    """a3d_jpeg_decode into caller-owned buffers (no synchronisation).  rgb uint8 [F,H,W,3] on the device (dense or a column range of
+    wider rows), status int32 [F]; data uint8 on the device, a multiple of 4 bytes holding `data_bytes` of units; meta a contiguous
+    int32 numpy array [unit_off (n_units+1) | frame_unit (F+1) | frame_ri (F) | frame_set (F)] and sets a uint8 numpy array
+    [n_sets, JPEG_TABSET_BYTES], each with its device copy; coef / planes scratch of F x jpeg_decode_scratch elements."""
+    import numpy as np
+
+    F_, H, W, pitch = _pitched_frames(rgb)
+    ce, pe = jpeg_decode_scratch(H, W, ncomp, hs, vs)
+    meta, sets = np.ascontiguousarray(meta, np.int32), np.ascontiguousarray(sets, np.uint8)
+    n_units = int(n_units)
+    if (meta.size != n_units + 1 + 3 * F_ + 1 or sets.ndim != 2 or sets.shape[1] != _lib.JPEG_TABSET_BYTES or _req(meta_dev, torch.int32).numel() < meta.size
+            or _req(sets_dev, torch.uint8).numel() < sets.size or _req(data, torch.uint8).numel() < (int(data_bytes) + 3) // 4 * 4
+            or _req(coef, torch.int16).numel() < F_ * ce or _req(planes, torch.uint8).numel() < F_ * pe or _req(status, torch.int32).numel() < F_):
+        raise ValueError("a buffer of a3d_jpeg_decode is smaller than the call needs")
+    d = _lib.JpegDecodeDesc()
+    d.F, d.H, d.W, d.pitch, d.ncomp, d.hs, d.vs, d.n_units, d.n_sets, d.data_bytes = F_, H, W, pitch, int(ncomp), int(hs), int(vs), n_units, sets.shape[0], int(data_bytes)
+    ip, at = C.POINTER(C.c_int), meta.ctypes.data
+    d.unit_off, d.frame_unit = C.cast(at, ip), C.cast(at + 4 * (n_units + 1), ip)
+    d.frame_ri, d.frame_set = C.cast(at + 4 * (n_units + 1 + F_ + 1), ip), C.cast(at + 4 * (n_units + 1 + 2 * F_ + 1), ip)
+    d.sets = C.cast(sets.ctypes.data, C.POINTER(C.c_ubyte))
+    d.d_data, d.d_meta, d.d_sets, d.coef, d.planes, d.rgb, d.status = _p(data), _p(meta_dev), _p(sets_dev), _p(coef), _p(planes), _p(rgb), _p(status)
+    _lib.check(_lib.lib().a3d_jpeg_decode(C.byref(d), _stream()), "a3d_jpeg_decode")

@@ -10,22 +10,34 @@ headers (once per size and quality) and the container; only the compressed bytes
     render_clip_jpeg(frames_u8, preds_raw, preds_opt)    -> yields list[bytes] per chunk: render_clip's rows, encoded
     MJPEGWriter(path, width, height, fps)                -> .write(jpeg), .close(); a context manager
 
+and the way back, for clips and JPEG frames as input (a3d_jpeg_decode, csrc/jpeg_decode.hip; the law in include/a3d.h and
+tests/jpeg_decode_ref.py): baseline JPEG, grey or 4:4:4 / 4:2:2 / 4:2:0, any tables, any restart interval, decoded on the GPU to the
+bytes libjpeg's default decoder gives.
+
+    jpeg_parse(data)                                     -> JPEGInfo (pure Python); ValueError for what the decoder's law leaves out
+    jpeg_decode(jpegs, device, chunk, strict)            -> uint8 [F,H,W,3] RGB on the device
+    MJPEGReader(path)                                    -> .width, .height, .fps, len(), reader[i], reader[a:b]; a context manager
+
 The container is a plain RIFF `AVI ` file (hdrl: avih + one strl of type vids / MJPG with a BITMAPINFOHEADER; a movi list of 00dc
 chunks; idx1), which ends at 2 GiB: the writer refuses a clip that would pass 1 GiB.  OpenDML is not written.
 """
 from __future__ import annotations
 
+import dataclasses
 import functools
+import re
 import struct
 from fractions import Fraction
 from typing import Iterator, List, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib, opt_ops
 
 ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
           35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+_UNZIG = tuple(ZIGZAG.index(n) for n in range(64))  # place in zigzag order of the coefficient at natural index n
 MAX_AVI_BYTES = 1 << 30
 
 
@@ -226,6 +238,370 @@ class MJPEGWriter:
     @property
     def frames(self) -> int:
         return len(self._index)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# reading: baseline JPEG files and Motion-JPEG clips, decoded on the GPU (a3d_jpeg_decode, csrc/jpeg_decode.hip; the law is stated
+# in include/a3d.h and, in numpy, in tests/jpeg_decode_ref.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_NOT_DATA = re.compile(b"\xff[^\x00\xd0-\xd7]")  # in entropy-coded data FF is followed by 00 or, as a restart marker, by D0 .. D7
+_RST = re.compile(b"\xff[\xd0-\xd7]")
+JPEG_STATUS = {_lib.JPEG_RANGE: "RANGE", _lib.JPEG_BAD_CODE: "BAD_CODE", _lib.JPEG_SHORT: "SHORT"}
+
+
+@dataclasses.dataclass(frozen=True)
+class JPEGInfo:
+    """What jpeg_parse learns from a file's headers.  quant: per component 64 bytes in natural order; huff: per component (DC bits[16],
+    DC vals, AC bits[16], AC vals); restart: MCUs per restart interval, 0 = none; scan: the byte range of the entropy-coded data;
+    units: the byte range of every unit (a restart interval, or the whole scan), markers excluded."""
+    height: int
+    width: int
+    ncomp: int
+    hs: int
+    vs: int
+    quant: tuple
+    huff: tuple
+    restart: int
+    scan: tuple
+    units: tuple
+
+    @property
+    def geometry(self):
+        return self.height, self.width, self.ncomp, self.hs, self.vs
+
+    @property
+    def mcus(self) -> int:
+        return -(-self.width // (8 * self.hs)) * -(-self.height // (8 * self.vs))
+
+    @property
+    def n_units(self) -> int:
+        """Units the geometry asks for (a damaged stream may hold fewer or more)."""
+        return -(-self.mcus // self.restart) if self.restart else 1
+
+    def table_set(self) -> bytes:
+        """One table set of a3d_jpeg_decode: _lib.JPEG_TABSET_BYTES bytes."""
+        out = b"".join(self.quant) + bytes(64 * (3 - self.ncomp))
+        for dc_bits, dc_vals, ac_bits, ac_vals in self.huff:
+            out += dc_bits + dc_vals.ljust(256, b"\0") + ac_bits + ac_vals.ljust(256, b"\0")
+        return out.ljust(_lib.JPEG_TABSET_BYTES, b"\0")
+
+
+@functools.lru_cache(maxsize=1)
+def _annex_k():
+    bits, vals = opt_ops.jpeg_tables()
+    n = _lib.JPEG_HUFF_VALS
+    return {key: (bits[16 * t:16 * t + 16], vals[n * t:n * t + sum(bits[16 * t:16 * t + 16])])
+            for t, key in enumerate(((0, 0), (1, 0), (0, 1), (1, 1)))}  # (class, id): DC0, AC0, DC1, AC1
+
+
+def jpeg_parse(data: bytes) -> JPEGInfo:
+    """The headers of one JPEG file.  Pure Python, one pass over the marker segments and one search over the scan.  Raises ValueError,
+    naming the cause, for everything a3d_jpeg_decode's law leaves out: progressive (SOF2), arithmetic coding, 12-bit, 16-bit
+    quantisation tables, sampling factors other than 4:4:4 / 4:2:2 / 4:2:0, more than one scan, 2 or 4 components, H or W outside
+    1 .. 65535, a missing SOI, SOF or SOS.  A file without any DHT segment gets the Annex K tables (the AVI "MJPG" convention)."""
+    data = bytes(data)
+    if data[:2] != b"\xff\xd8":
+        raise ValueError("not a JPEG file: it does not start with SOI")
+    quant, huff, sof, restart, sos, adobe = {}, {}, None, 0, None, None
+    at, n_data = 2, len(data)
+    while at + 4 <= n_data:
+        if data[at] != 0xFF:
+            raise ValueError(f"byte {at}: expected a marker")
+        m = data[at + 1]
+        if m == 0xFF:  # fill byte
+            at += 1
+            continue
+        if m == 0xD9:
+            break
+        size = (data[at + 2] << 8) | data[at + 3]
+        body = data[at + 4:at + 2 + size]
+        at += 2 + size
+        if m == 0xDB:
+            while body:
+                if body[0] >> 4:
+                    raise ValueError("16-bit quantisation table")
+                if len(body) < 65:
+                    raise ValueError("DQT segment cut short")
+                quant[body[0] & 15] = bytes(body[1 + z] for z in _UNZIG)  # zigzag in the file, natural order here
+                body = body[65:]
+        elif m == 0xC4:
+            while body:
+                if len(body) < 17 or len(body) < 17 + sum(body[1:17]) or sum(body[1:17]) > 256:
+                    raise ValueError("DHT segment cut short")
+                n = sum(body[1:17])
+                huff[(body[0] >> 4, body[0] & 15)] = (body[1:17], body[17:17 + n])
+                body = body[17 + n:]
+        elif m == 0xDD:
+            restart = int.from_bytes(body[:2], "big")
+        elif m == 0xEE and body[:5] == b"Adobe" and len(body) >= 12:
+            adobe = body[11]
+        elif m == 0xC0:
+            if sof is not None:
+                raise ValueError("more than one frame header")
+            sof = body
+        elif m == 0xC2:
+            raise ValueError("progressive JPEG (SOF2)")
+        elif 0xC1 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            raise ValueError(f"SOF{m - 0xC0}: arithmetic coding" if m >= 0xC9 else f"SOF{m - 0xC0}: not baseline (12-bit, lossless or hierarchical)")
+        elif m == 0xDA:
+            if sof is None:
+                raise ValueError("no SOF marker in front of SOS")
+            sos = (body, at)
+            break
+    if sof is None:
+        raise ValueError("no SOF marker")
+    if sos is None:
+        raise ValueError("no SOS marker")
+    if len(sof) < 6 or len(sof) < 6 + 3 * sof[5]:
+        raise ValueError("SOF segment cut short")
+    precision, height, width, ncomp = sof[0], (sof[1] << 8) | sof[2], (sof[3] << 8) | sof[4], sof[5]
+    if precision != 8:
+        raise ValueError(f"{precision}-bit samples")
+    if ncomp not in (1, 3):
+        raise ValueError(f"{ncomp} components: grey or Y / Cb / Cr only")
+    if not (1 <= height <= 65535 and 1 <= width <= 65535):
+        raise ValueError(f"{height} x {width}: a JPEG is 1 .. 65535 pixels a side")
+    if ncomp == 3 and adobe == 0:
+        raise ValueError("Adobe transform 0: RGB, not Y / Cb / Cr")
+    body, lo = sos
+    if not body or body[0] != ncomp or len(body) < 4 + 2 * ncomp:
+        raise ValueError("more than one scan (the first one does not hold every component)")
+    selectors = {body[1 + 2 * i]: body[2 + 2 * i] for i in range(ncomp)}
+    if tuple(body[1 + 2 * ncomp:4 + 2 * ncomp]) != (0, 63, 0):
+        raise ValueError("not a sequential scan")
+    sampling, q_out, h_out = [], [], []
+    for i in range(ncomp):
+        cid, hv, tq = sof[6 + 3 * i:9 + 3 * i]
+        if cid not in selectors:
+            raise ValueError("more than one scan (the first one does not hold every component)")
+        if tq not in quant:
+            raise ValueError(f"quantisation table {tq} is missing")
+        tabs = ()
+        for cls, tid in ((0, selectors[cid] >> 4), (1, selectors[cid] & 15)):
+            if (cls, tid) in huff:
+                tabs += huff[(cls, tid)]
+            elif not huff and tid < 2:
+                tabs += _annex_k()[(cls, tid)]
+            else:
+                raise ValueError(f"Huffman table {cls}/{tid} is missing")
+        sampling.append((hv >> 4, hv & 15))
+        q_out.append(quant[tq])
+        h_out.append(tabs)
+    if ncomp == 1:
+        sampling = [(1, 1)]  # a scan of one component is never interleaved: its MCU is one block
+    elif sampling[1:] != [(1, 1), (1, 1)] or sampling[0] not in ((1, 1), (2, 1), (2, 2)):
+        raise ValueError("sampling factors " + ", ".join(f"{h}x{v}" for h, v in sampling) + ": 4:4:4, 4:2:2 and 4:2:0 only")
+    end = _NOT_DATA.search(data, lo)
+    hi = end.start() if end else n_data
+    if end and data[hi + 1] != 0xD9 and data.find(b"\xff\xda", hi) >= 0:
+        raise ValueError("more than one scan")
+    units, start = [], lo
+    if restart:
+        for m in _RST.finditer(data, lo, hi):
+            units.append((start, m.start()))
+            start = m.end()
+    units.append((start, hi))
+    return JPEGInfo(height, width, ncomp, sampling[0][0], sampling[0][1], tuple(q_out), tuple(h_out), restart, (lo, hi), tuple(units))
+
+
+def jpeg_decode(jpegs: Sequence[bytes], device="cuda", chunk: int = 8, strict: bool = True):
+    """F baseline JPEG files of one size and one sampling -> uint8 [F,H,W,3] RGB on the device, byte for byte what libjpeg's
+    default decoder returns (include/a3d.h states the law).  The host parses the headers and uploads the entropy-coded bytes and one table set per
+    distinct set of tables of the call; `chunk` frames are decoded per a3d_jpeg_decode call, and the host prepares a chunk while the
+    device decodes the one before.  A frame's pixels do not depend on the frames beside it or on `chunk`.  With `strict` a frame
+    whose status is not 0 raises ValueError with its index and the code (SHORT, BAD_CODE, RANGE); without, -> (frames, status
+    int32 [F] on the host)."""
+    infos = []
+    for i, j in enumerate(jpegs):
+        try:
+            infos.append(jpeg_parse(j))
+        except ValueError as e:
+            raise ValueError(f"frame {i}: {e}") from None
+    if not infos:
+        raise ValueError("jpeg_decode: no frames")
+    for i, info in enumerate(infos):
+        if info.geometry != infos[0].geometry:
+            raise ValueError(f"frame {i} is {info.geometry} (H, W, components, luma sampling), frame 0 is {infos[0].geometry}: one call decodes one geometry")
+    H, W, ncomp, hs, vs = infos[0].geometry
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"device {device!r}: the decoder runs on the GPU")
+    F = len(infos)
+    chunk = max(1, min(int(chunk), F))
+    set_index, set_of = {}, []
+    for info in infos:
+        set_of.append(set_index.setdefault(info.table_set(), len(set_index)))
+    sets = np.frombuffer(b"".join(set_index), np.uint8).reshape(len(set_index), _lib.JPEG_TABSET_BYTES)
+    ce, pe = opt_ops.jpeg_decode_scratch(H, W, ncomp, hs, vs)
+    with torch.cuda.device(dev):
+        sets_dev = torch.from_numpy(sets.copy()).to(dev)
+        coef = torch.empty(chunk * ce, dtype=torch.int16, device=dev)
+        planes = torch.empty(chunk * pe, dtype=torch.uint8, device=dev)
+        out = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+        status = torch.empty(F, dtype=torch.int32, device=dev)
+        for lo in range(0, F, chunk):
+            hi = min(lo + chunk, F)
+            pieces, unit_off, frame_unit = [], [0], [0]
+            for k in range(lo, hi):
+                info, data = infos[k], jpegs[k]
+                ranges = (list(info.units) + [(0, 0)] * info.n_units)[:info.n_units]  # a damaged stream: empty units for the missing ones
+                for a, b in ranges:
+                    pieces.append(data[a:b])
+                    unit_off.append(unit_off[-1] + b - a)
+                frame_unit.append(len(unit_off) - 1)
+            total = unit_off[-1]
+            if total > 0x7FFFFFFF:
+                raise ValueError(f"frames {lo} .. {hi - 1} hold {total} bytes: more than one call takes, pass a smaller chunk")
+            blob = np.frombuffer(b"".join(pieces) + bytes(-total % 4 + 4), np.uint8)
+            meta = np.array(unit_off + frame_unit + [i.restart for i in infos[lo:hi]] + set_of[lo:hi], np.int32)
+            opt_ops.jpeg_decode_into(out[lo:hi], status[lo:hi], torch.from_numpy(blob.copy()).to(dev), total, meta, torch.from_numpy(meta).to(dev), sets,
+                                     sets_dev, len(unit_off) - 1, ncomp, hs, vs, coef, planes)
+        st = status.cpu()
+    if not strict:
+        return out, st
+    bad = torch.nonzero(st).flatten().tolist()
+    if bad:
+        raise ValueError(f"frame {bad[0]}: status {JPEG_STATUS.get(int(st[bad[0]]), int(st[bad[0]]))}" +
+                         (f" (and {len(bad) - 1} more frames)" if len(bad) > 1 else ""))
+    return out
+
+
+class MJPEGReader:
+    """The frames of a Motion-JPEG RIFF `AVI ` file, as bytes: reader[i], reader[a:b], len(reader), iteration; .width, .height, .fps (a
+    Fraction, dwRate / dwScale of the stream header).  Opening reads hdrl and idx1 (or, without an index, the eight-byte headers of
+    the movi list); a frame's bytes are read when it is asked for.  The first stream must be video with the handler MJPG; OpenDML
+    files (a second RIFF chunk of type AVIX) are refused, as the writer refuses to write them."""
+
+    def __init__(self, path):
+        self._f = open(path, "rb")
+        try:
+            self._open()
+        except Exception:
+            self._f.close()
+            raise
+
+    def _open(self):
+        f = self._f
+        size = f.seek(0, 2)
+        f.seek(0)
+        head = f.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"AVI ":
+            raise ValueError("not a RIFF AVI file")
+        riff_end = min(8 + struct.unpack("<I", head[4:8])[0], size)
+        if riff_end + 12 <= size:
+            f.seek(riff_end + (riff_end & 1))
+            more = f.read(12)
+            if more[:4] == b"RIFF" and more[8:12] == b"AVIX":
+                raise ValueError("OpenDML AVI (an AVIX chunk follows the first RIFF chunk): not read")
+        hdrl = movi = idx1 = None
+        at = 12
+        while at + 8 <= riff_end:
+            f.seek(at)
+            cc, n = struct.unpack("<4sI", f.read(8))
+            if cc == b"LIST":
+                kind = f.read(4)
+                if kind == b"hdrl":
+                    hdrl = f.read(n - 4)
+                elif kind == b"movi":
+                    movi = (at + 8, n)  # offset of the 'movi' fourcc, bytes from there
+            elif cc == b"idx1":
+                idx1 = f.read(n)
+            at += 8 + n + (n & 1)
+        if hdrl is None or movi is None:
+            raise ValueError("AVI file without a hdrl or a movi list")
+        self._parse_hdrl(hdrl)
+        self._frames = self._from_index(idx1, movi) if idx1 else None
+        if self._frames is None:
+            self._frames = self._walk(movi[0] + 4, min(movi[0] + movi[1], size))
+
+    def _parse_hdrl(self, hdrl: bytes):
+        at, strh, strf, avih = 0, None, None, None
+        while at + 8 <= len(hdrl):
+            cc, n = struct.unpack_from("<4sI", hdrl, at)
+            if cc == b"avih":
+                avih = struct.unpack_from("<14I", hdrl, at + 8)
+            elif cc == b"LIST" and hdrl[at + 8:at + 12] == b"strl" and strh is None:  # the first stream
+                sub, end = at + 12, at + 8 + n
+                while sub + 8 <= end:
+                    scc, sn = struct.unpack_from("<4sI", hdrl, sub)
+                    if scc == b"strh":
+                        strh = hdrl[sub + 8:sub + 8 + sn]
+                    elif scc == b"strf":
+                        strf = hdrl[sub + 8:sub + 8 + sn]
+                    sub += 8 + sn + (sn & 1)
+            at += 8 + n + (n & 1)
+        if avih is None or strh is None or len(strh) < 36 or strf is None or len(strf) < 20:
+            raise ValueError("AVI file without avih, strh or strf")
+        if strh[:4] != b"vids":
+            raise ValueError(f"the first stream is {strh[:4]!r}, not video")
+        handler, compression = strh[4:8], strf[16:20]
+        if handler.upper() != b"MJPG" or compression.upper() != b"MJPG":
+            raise ValueError(f"stream handler {handler!r} / compression {compression!r}: only MJPG (Motion-JPEG) is read")
+        scale, rate = struct.unpack_from("<II", strh, 20)
+        if not scale or not rate:
+            raise ValueError("stream header without a frame rate")
+        self.fps = Fraction(rate, scale)
+        self.width, self.height = struct.unpack_from("<ii", strf, 4)
+        self.height = abs(self.height)
+
+    def _from_index(self, idx1: bytes, movi):
+        """idx1 entries of the first stream -> [(offset of the data, length)].  Offsets count from the 'movi' fourcc (the format) or from
+        the start of the file (some writers): whichever makes the first entry point at its chunk header.  None if neither does."""
+        entries = [struct.unpack_from("<4sIII", idx1, 16 * i) for i in range(len(idx1) // 16)]
+        entries = [(off, n) for cc, _flags, off, n in entries if cc in (b"00dc", b"00db")]
+        if not entries:
+            return []
+        for base in (movi[0], 0):
+            self._f.seek(base + entries[0][0])
+            if self._f.read(8) == b"00dc" + struct.pack("<I", entries[0][1]):
+                return [(base + off + 8, n) for off, n in entries]
+        return None
+
+    def _walk(self, lo: int, hi: int):
+        out, at = [], lo
+        while at + 8 <= hi:
+            self._f.seek(at)
+            cc, n = struct.unpack("<4sI", self._f.read(8))
+            if cc == b"LIST":  # 'rec ' groups: step inside
+                at += 12
+                continue
+            if cc in (b"00dc", b"00db"):
+                out.append((at + 8, n))
+            at += 8 + n + (n & 1)
+        return out
+
+    def __len__(self) -> int:
+        return len(self._frames)
+
+    def _read(self, k: int) -> bytes:
+        off, n = self._frames[k]
+        self._f.seek(off)
+        return self._f.read(n)
+
+    def __getitem__(self, key):
+        if self._f is None:
+            raise ValueError("read from a closed MJPEGReader")
+        if isinstance(key, slice):
+            return [self._read(k) for k in range(*key.indices(len(self)))]
+        k = key + len(self) if key < 0 else key
+        if not 0 <= k < len(self):
+            raise IndexError(key)
+        return self._read(k)
+
+    def __iter__(self):
+        return (self[k] for k in range(len(self)))
+
+    def close(self) -> None:
+        if self._f is not None:
+            self._f.close()
+            self._f = None
 
     def __enter__(self):
         return self

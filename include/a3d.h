@@ -1172,6 +1172,82 @@ int a3d_jpeg_encode(const unsigned char *frames, int F, int H, int W, int pitch,
 int a3d_jpeg_pack(const unsigned char *slots, const int *seg_off, const int *seg_len, int F, int H, int W, unsigned char *packed,
                   long long packed_bytes, void *stream);
 
+/* ================================================================================================
+ * JPEG decode: the entropy-coded bytes of F baseline JPEG frames of one geometry -> uint8 [F,H,pitch,3] RGB on the device, byte for
+ * byte what libjpeg's default decoder (PIL's Image.open(f).convert("RGB")) returns.  The host (articulation3d_amd/video.py) parses the
+ * headers, finds every unit's bytes and refuses what is outside the law.  Integer arithmetic only.
+ *
+ * The law (held byte for byte by tests/jpeg_decode_ref.py, which tests/test_jpeg_decode_host.py holds to libjpeg):
+ *   accepted  SOF0, 8-bit, one interleaved scan.  One component (grey, returned as R = G = B) or three (Y, Cb, Cr) with chroma 1x1
+ *             and luma hs x vs = 1x1, 2x1 or 2x2 (4:4:4, 4:2:2, 4:2:0).  8-bit quantisation tables.  Any Huffman tables; a file
+ *             without any DHT segment uses the Annex K tables of a3d_jpeg_tables (the AVI "MJPG" convention).  Any restart
+ *             interval, or none.  The host refuses everything else: progressive, arithmetic, 12-bit, 16-bit quantisation tables,
+ *             other sampling factors, several scans, 2 or 4 components, H or W outside 1 .. 65535, a missing SOI, SOF or SOS.
+ *   geometry  an MCU is 8 hs x 8 vs pixels; there are mx = ceil(W / 8 hs) by my = ceil(H / 8 vs) MCUs in raster order; within an MCU
+ *             each component contributes its v x h blocks in raster order.  A unit is one restart interval of n MCUs (the last one
+ *             of a frame is short; intervals need not align with MCU rows), or the whole scan when n = 0: ceil(mx my / n) units per
+ *             frame.  The DC predictors are zero at the start of every unit.  In entropy-coded data FF 00 is the data byte FF, and
+ *             FF D0 .. D7 occurs only as a restart marker, which the host removes.
+ *   entropy   symbol, run / size, ZRL, EOB and one's-complement extension as in the standard; a DC value accumulates modulo 2^16.
+ *             A unit that needs bits past its byte range reads zeros and makes the frame A3D_JPEG_SHORT.  A bit pattern that matches
+ *             no code of at most 16 bits, a DC symbol above 15, or a run that passes coefficient 63 (a ZRL that ends past 64
+ *             included) makes it A3D_JPEG_BAD_CODE and ends the unit; its remaining blocks stay zero.  A unit writes only its own
+ *             blocks: no stream content can make a read or a write leave the buffers of the call.
+ *   IDCT      libjpeg's jidctint ("islow") on dequantised coefficients, CONST_BITS 13, PASS1_BITS 2, constants 2446, 3196, 4433,
+ *             6270, 7373, 9633, 12299, 15137, 16069, 16819, 20995, 25172: pass 1 over columns descales by 11, pass 2 over rows
+ *             by 18, sample = clamp(v + 128, 0, 255) (a plain clamp).
+ *   domain    the law holds for frames in which every dequantised coefficient and every pass-1 output is within +-16383: the
+ *             absolute gain of a pass over all its intermediates is 61 214, and 61 214 x 16 383 < 2^31, so everything fits int32.
+ *             Outside, libjpeg's own routines disagree with each other: the frame is A3D_JPEG_RANGE and its pixels are unspecified
+ *             (real encoders stay about four times below the bound).
+ *   upsample  libjpeg's "fancy" filters.  dw = ceil(W / hs), dh = ceil(H / vs) is the chroma plane's true size; neighbour indices
+ *             are clamped to [0, dw-1] and [0, dh-1].
+ *             2x1:  out[2i] = (3 in[i] + in[i-1] + 1) >> 2,  out[2i+1] = (3 in[i] + in[i+1] + 2) >> 2.
+ *             2x2:  s = 3 near + far vertically (an even output row takes the row above as far, an odd one the row below), then
+ *                   out[2i] = (3 s[i] + s[i-1] + 8) >> 4,  out[2i+1] = (3 s[i] + s[i+1] + 7) >> 4.
+ *             A chroma plane with dw <= 2 is replicated instead, in both directions.
+ *   colour    R = Y + ((91881 Cr' + 32768) >> 16),  G = Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16),
+ *             B = Y + ((116130 Cb' + 32768) >> 16),  Cb' = Cb - 128, Cr' = Cr - 128, >> arithmetic, clamped to 0 .. 255.
+ *   status    per frame, the largest that occurred of 0 < A3D_JPEG_RANGE < A3D_JPEG_BAD_CODE < A3D_JPEG_SHORT: the cause, not its
+ *             consequences (zeros read past a unit may match no code; a unit cut short leaves garbage coefficients).
+ * The result of a frame does not depend on F or on the frames beside it.
+ * ============================================================================================== */
+#define A3D_JPEG_RANGE 1
+#define A3D_JPEG_BAD_CODE 2
+#define A3D_JPEG_SHORT 3
+/* One table set: quant [3][64] (per component, natural order), then per component its DC and its AC Huffman specification, each
+ * bits[16] + vals[256] (zero-filled past the table's symbols).  Specifications, not lookups: the kernel builds its own form. */
+#define A3D_JPEG_TABSET_BYTES (192 + 6 * (16 + 256))
+/* Elements PER FRAME of the two scratch buffers of a3d_jpeg_decode: coef (int16; a frame's status word in its last 16 bytes) and
+ * planes (uint8, the components at their padded sizes).  A3D_ERR_ARG for a geometry outside the law. */
+int a3d_jpeg_decode_scratch(int H, int W, int ncomp, int hs, int vs, size_t *coef_elems, size_t *plane_elems);
+typedef struct {
+    int F, H, W, pitch;          /* rgb is [F,H,pitch,3], pitch >= W pixels per row                                          */
+    int ncomp, hs, vs;           /* 1 or 3 components; the luma sampling factors                                             */
+    int n_units, n_sets;
+    long long data_bytes;        /* all units of all frames, concatenated without their markers, still stuffed              */
+    /* HOST, read before any launch: */
+    const int *unit_off;         /* [n_units+1] unit u is bytes unit_off[u] .. unit_off[u+1] of the data                     */
+    const int *frame_unit;       /* [F+1] frame f owns units frame_unit[f] .. frame_unit[f+1]                                */
+    const int *frame_ri;         /* [F] restart interval in MCUs, 0 = none                                                  */
+    const int *frame_set;        /* [F] index of the frame's table set                                                      */
+    const unsigned char *sets;   /* [n_sets][A3D_JPEG_TABSET_BYTES]                                                         */
+    /* DEVICE: */
+    const unsigned char *d_data; /* data_bytes rounded up to a multiple of 4 are readable; 4-byte aligned                    */
+    const int *d_meta;           /* the four host tables in the order above, back to back                                    */
+    const unsigned char *d_sets; /* `sets` on the device, 8-byte aligned                                                    */
+    short *coef;                 /* scratch, F * coef_elems, 16-byte aligned                                                 */
+    unsigned char *planes;       /* scratch, F * plane_elems, 8-byte aligned                                                 */
+    unsigned char *rgb;          /* out; bytes of a row past W pixels are left alone                                         */
+    int *status;                 /* out [F]                                                                                  */
+} a3d_jpeg_decode_desc;
+/* One memset and three launches (entropy, dequantise + IDCT, upsample + colour) on the stream, no synchronisation.  The kernels read
+ * the device copies and clamp whatever they find there.  A3D_ERR_ARG before any launch: a null pointer, a misaligned buffer, a
+ * geometry outside the law, pitch < W, F outside 0 .. 65535, an offset table that is not monotonic or does not start at 0 and end
+ * at data_bytes / n_units, a frame whose unit count is not ceil(mx my / interval), a table index out of range, a Huffman
+ * specification whose codes do not fit their lengths, or data_bytes above 2^31 - 1.  F == 0 is a no-op. */
+int a3d_jpeg_decode(const a3d_jpeg_decode_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

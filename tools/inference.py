@@ -8,9 +8,14 @@ build the `create_instances` records, `track_planes`, `optimize_planes(preds, pl
 batched, frame-sharded `pipeline.detect_clip` (one RCCL all-gather per clip when launched with torchrun) and the
 optimiser's sweeps run on the GPU.  `random.seed(2020)` / `np.random.seed(2020)` as in the reference (:172-173).
 
-Input (this image has no video decoder: cv2 / imageio are absent, so .mp4 is refused with a clear message):
+Input (this image has no H.264 decoder: cv2 / imageio are absent, so .mp4 / .mov are refused with a clear message):
   * a .npy / .npz file with uint8 frames [F,H,W,3] in RGB order (what imageio would hand over), or
-  * a directory of .png / .jpg frames (decoded with PIL, sorted by name), or
+  * a Motion-JPEG .avi (what `--vis avi` writes, and what cameras and ffmpeg -c:v mjpeg write): the frames are baseline JPEG, decoded
+    on the GPU (articulation3d_amd/video.py: MJPEGReader + jpeg_decode) to the bytes PIL's libjpeg gives; `--fps` defaults to the
+    container's rate, or
+  * a directory of .png / .jpg frames, sorted by name: baseline JPEG files of one size go through the same GPU decoder, everything
+    else (PNG, progressive or otherwise refused files, frames the decoder flags) through PIL -- `--decoder auto|gpu|pil`, the frames
+    are the same bytes under all three, or
   * `synthetic:N` / `synthetic:NxHxW` -- N seeded random frames (plumbing check), optionally at a source size H x W.
 The frames go to the GPU as they come from the reader (uint8 RGB, any size): the reference's `cv2.resize(im, (640, 480))` and
 BGR flip (:216-218) run on the device, fused with the normalisation in front of the stem (a3d_preprocess_resize_u8).
@@ -51,12 +56,60 @@ def count_frames(path: str) -> int:
         return int(z[list(z.keys())[0]].shape[0])
     if os.path.isdir(path):
         return len([n for n in os.listdir(path) if n.lower().endswith((".png", ".jpg", ".jpeg"))])
+    if path.lower().endswith(".avi"):
+        from articulation3d_amd.video import MJPEGReader
+
+        with MJPEGReader(path) as reader:
+            return len(reader)
     return 1
 
 
-def read_frames(path: str, lo: int = 0, hi: int = None) -> np.ndarray:
+def gpu_decodes(info, decoder: str) -> bool:
+    """Whether a stream that jpeg_parse accepts goes to the GPU.  `gpu`: always.  `auto`: the classes that MEASUREMENTS.md ("JPEG decode")
+    found faster there than PIL on one host thread -- streams with restart intervals; a scan without them is one sequential
+    Huffman walk, which one GPU lane does more slowly than one CPU core."""
+    return decoder == "gpu" or (decoder == "auto" and info.restart > 0)
+
+
+def decode_images(blobs, decoder: str = "auto") -> np.ndarray:
+    """Encoded images (the bytes of .jpg / .png files or of an AVI's chunks) -> uint8 [n,H,W,3] RGB.  Baseline JPEG streams that share the
+    size and sampling of the first such stream are decoded on the GPU in one jpeg_decode call, the rest by PIL -- as is every frame the
+    GPU decoder flags (a damaged or out-of-domain stream), so the result is PIL's under every setting of `decoder`."""
+    import io
+
+    from PIL import Image
+
+    frames = [None] * len(blobs)
+    if decoder != "pil":
+        from articulation3d_amd.video import jpeg_decode, jpeg_parse
+
+        chosen, geometry = [], None
+        for k, blob in enumerate(blobs):
+            if blob[:2] != b"\xff\xd8":
+                continue
+            try:
+                info = jpeg_parse(blob)
+            except ValueError:
+                continue
+            if gpu_decodes(info, decoder) and geometry in (None, info.geometry):
+                geometry = info.geometry
+                chosen.append(k)
+        if chosen:
+            out, status = jpeg_decode([blobs[k] for k in chosen], chunk=32, strict=False)
+            out = out.cpu().numpy()
+            for i, k in enumerate(chosen):
+                if int(status[i]) == 0:
+                    frames[k] = out[i]
+    for k, blob in enumerate(blobs):
+        if frames[k] is None:
+            frames[k] = np.asarray(Image.open(io.BytesIO(blob)).convert("RGB"))
+    return np.stack(frames)
+
+
+def read_frames(path: str, lo: int = 0, hi: int = None, decoder: str = "auto") -> np.ndarray:
     """-> uint8 [hi-lo,Hs,Ws,3] RGB at the SOURCE size (no host-side resize): frames lo .. hi-1 of the clip (default: all).  Under
-    torchrun every rank reads only its own block (memory-mapped .npy, per-file image decode)."""
+    torchrun every rank reads only its own block (memory-mapped .npy, the AVI's index, per-file image decode).  `decoder`: who decodes
+    JPEG streams (decode_images)."""
     from PIL import Image
 
     sl = slice(lo, hi)
@@ -67,8 +120,17 @@ def read_frames(path: str, lo: int = 0, hi: int = None) -> np.ndarray:
         spec = path.split(":")[1].split("x")
         n, h, w = int(spec[0]), (int(spec[1]) if len(spec) == 3 else 480), (int(spec[2]) if len(spec) == 3 else 640)
         return synthetic_frames(n, h=h, w=w)[sl][..., ::-1].copy()  # generated BGR -> RGB, flipped back on the device
-    if path.endswith((".mp4", ".avi", ".mov")):
+    if path.endswith((".mp4", ".mov")):
         raise SystemExit("no video decoder in this environment (cv2 / imageio absent): pass a .npy of RGB frames or a directory of images")
+    if path.lower().endswith(".avi"):
+        from articulation3d_amd.video import MJPEGReader
+
+        try:
+            with MJPEGReader(path) as reader:
+                blobs, size = reader[sl], (reader.height, reader.width)
+        except ValueError as e:
+            raise SystemExit(f"{path}: {e} (only Motion-JPEG .avi files are read)")
+        return decode_images(blobs, decoder) if blobs else np.zeros((0, *size, 3), np.uint8)
     if path.endswith(".npy"):
         frames = np.load(path, mmap_mode="r")[sl]
     elif path.endswith(".npz"):
@@ -78,7 +140,11 @@ def read_frames(path: str, lo: int = 0, hi: int = None) -> np.ndarray:
         every = sorted(n for n in os.listdir(path) if n.lower().endswith((".png", ".jpg", ".jpeg")))
         names = every[sl]
         if names:
-            frames = np.stack([np.asarray(Image.open(os.path.join(path, n)).convert("RGB")) for n in names])
+            blobs = []
+            for n in names:
+                with open(os.path.join(path, n), "rb") as f:
+                    blobs.append(f.read())
+            frames = decode_images(blobs, decoder)
         else:  # an empty block (trailing ranks when F <= ceil(F / world) * (world - 1)): zero frames at the clip's size
             if not every:
                 raise SystemExit(f"{path}: no .png / .jpg frames")
@@ -197,7 +263,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "<output>/output.avi, Motion-JPEG (baseline JPEG frames encoded on the GPU) in an AVI container -- not the reference's "
                          "H.264 .mp4, which needs an encoder this package does not have")
     ap.add_argument("--vis-quality", default=90, type=int, help="--vis avi: JPEG quality, 1 .. 100")
-    ap.add_argument("--fps", default="30", help="--vis avi: frames per second, an integer or a ratio such as 30000/1001")
+    ap.add_argument("--fps", default=None,
+                    help="--vis avi: frames per second, an integer or a ratio such as 30000/1001 (default: the rate of an .avi input, else 30)")
+    ap.add_argument("--decoder", choices=("auto", "gpu", "pil"), default="auto",
+                    help="who decodes JPEG input (.avi chunks, .jpg files): gpu = every baseline stream on the GPU, pil = PIL on the host, auto = "
+                         "the GPU for the streams it was measured to decode faster (those with restart intervals); the frames are the same bytes")
     ap.add_argument("--mask-alpha", default=0.0, type=float,
                     help="--vis: opacity of the instance masks on the seg panels (0 = none, as the reference draws them)")
     ap.add_argument("--save-obj", action="store_true",
@@ -216,6 +286,13 @@ def main():
     random.seed(2020)
     np.random.seed(2020)
     args = build_parser().parse_args()
+    if args.fps is None:
+        args.fps = "30"
+        if args.input.lower().endswith(".avi") and os.path.isfile(args.input):
+            from articulation3d_amd.video import MJPEGReader
+
+            with MJPEGReader(args.input) as reader:
+                args.fps = str(reader.fps)
 
     # one process per GPU under torchrun (frames sharded by pipeline.detect_clip, ONE all-gather of the records per clip):
     # rank / device / process group are set up before anything touches the GPU; rank 0 alone tracks, optimises and writes
@@ -259,11 +336,11 @@ def main():
 
     n_frames = count_frames(args.input)
     lo, hi = shard_range(n_frames, rank, world)
-    frames_rgb = read_frames(args.input, lo, hi)  # this rank's block only (rank 0 reads the rest later, for the optimiser)
+    frames_rgb = read_frames(args.input, lo, hi, args.decoder)  # this rank's block only (rank 0 reads the rest later, for the optimiser)
     if args.calibrate_bn:
         # the statistics come from the FIRST two frames of the clip on EVERY rank (rank 0's own block may hold only one of them)
         n_head = min(2, n_frames)
-        frames_rgb_head = frames_rgb[:n_head] if lo == 0 and hi - lo >= n_head else read_frames(args.input, 0, n_head)
+        frames_rgb_head = frames_rgb[:n_head] if lo == 0 and hi - lo >= n_head else read_frames(args.input, 0, n_head, args.decoder)
         from articulation3d_amd import ops
         from articulation3d_amd.utils.synthetic import calibrate_batchnorm
 
@@ -273,7 +350,7 @@ def main():
         # once per loaded checkpoint, on the FIRST two frames of the clip on every rank (every rank must pin the same layers: a frame's
         # result may not depend on the rank that detects it)
         n_head = min(2, n_frames)
-        head_rgb = frames_rgb[:n_head] if lo == 0 and hi - lo >= n_head else read_frames(args.input, 0, n_head)
+        head_rgb = frames_rgb[:n_head] if lo == 0 and hi - lo >= n_head else read_frames(args.input, 0, n_head, args.decoder)
         audit = model.audit_precision(torch.from_numpy(np.ascontiguousarray(head_rgb)).to(model.device), source_rgb=True)
         if rank == 0:
             worst = max((r["max_ratio"] for r in audit.rows), default=0.0)
@@ -287,7 +364,7 @@ def main():
         dist.destroy_process_group()
         if rank != 0:  # every rank holds the gathered detections; the temporal stage and the files are rank 0's
             return
-        frames_rgb = read_frames(args.input)  # the optimiser's sweeps look at the whole clip
+        frames_rgb = read_frames(args.input, decoder=args.decoder)  # the optimiser's sweeps look at the whole clip
     planes = track_planes(preds)
     raw_preds = snapshot_predictions(preds) if args.vis != "none" else None
     opt_preds = optimize_planes(preds, planes, "3dc", frames=frames_rgb)
