@@ -447,6 +447,7 @@ SIGNATURES = {
     "a3d_jpeg_pack": (C.c_int, [fptr, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, C.c_longlong, fptr]),
     "a3d_jpeg_decode_scratch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "a3d_jpeg_decode": (C.c_int, [C.POINTER(JpegDecodeDesc), fptr]),
+    "a3d_jpeg_decode_split": (C.c_int, [C.POINTER(JpegDecodeDesc), C.c_int, fptr]),
     "a3d_sgd_momentum": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_sgd_momentum_bf16g": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_f32_to_bf16_scaled": (C.c_int, [fptr, fptr, C.c_size_t, C.c_float, fptr]),

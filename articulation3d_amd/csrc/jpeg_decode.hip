@@ -8,6 +8,8 @@
 //             the 00 behind every FF, and writes each non-zero coefficient as int16 at its natural place in the zeroed scratch.  The
 //             lanes of a wave walk different streams, so their loops diverge, and a scan without restart intervals keeps one lane of
 //             one wave busy per frame: that is the price of the format, and MEASUREMENTS.md says what it costs.
+//             a3d_jpeg_decode_split launches jpeg_decode_split_kernel in its place: a unit is cut into subsequences that many lanes
+//             walk at once and that synchronise themselves ("entropy, self-synchronising" below); the other launches are the same.
 //   idct      32 blocks per workgroup, 8 lanes per block.  Lane r loads row r (one 16-byte load) and dequantises it, lane j transforms
 //             column j, lane r transforms row r and stores its 8 samples as one 8-byte word; rows meet columns in LDS (rows padded to 9
 //             words).  The domain test of the law is taken here and raised into the frame's status word.
@@ -154,21 +156,11 @@ __device__ __forceinline__ bool decode_block(bit_reader &rd, short *__restrict__
     return true;
 }
 
-// Units per workgroup.  A wave runs the distinct paths of its live lanes one after the other, so fewer lanes per wave buy less
-// serialisation at the price of more table builds: 16 was measured against 64 (MEASUREMENTS.md, "JPEG decode").
-constexpr int EN_LANES = 16;
-
-__global__ __launch_bounds__(EN_LANES) void jpeg_decode_entropy_kernel(const unsigned int *__restrict__ data, const int *__restrict__ meta,
-                                                                       const unsigned char *__restrict__ sets, short *__restrict__ coef,
-                                                                       const dec_geom g) {
-    __shared__ huff_lds T[6];
-    __shared__ unsigned char zig[64];
-    const int lane = threadIdx.x, f = blockIdx.y;
-    const int *unit_off = meta, *frame_unit = meta + g.n_units + 1, *frame_ri = frame_unit + g.F + 1, *frame_set = frame_ri + g.F;
-    const int set = min(max(frame_set[f], 0), g.n_sets - 1);
-    const unsigned char *spec = sets + (size_t)set * A3D_JPEG_TABSET_BYTES + SET_QUANT;
-    const int n_tab = 2 * g.ncomp;
-    for (int i = lane; i < 64; i += EN_LANES) zig[i] = k_zigzag[i];
+// The workgroup's form of a frame's Huffman specifications (`spec`: n_tab of them, bits[16] + vals[256] each) and the zig-zag order, in
+// LDS: every one of the workgroup's `lanes` threads calls it.  It ends behind a barrier.
+__device__ __forceinline__ void build_tables(huff_lds *T, unsigned char *zig, const unsigned char *__restrict__ spec, const int n_tab, const int lane,
+                                             const int lanes) {
+    for (int i = lane; i < 64; i += lanes) zig[i] = k_zigzag[i];
     if (lane < n_tab) {
         const unsigned char *bits = spec + lane * SET_TABLE;
         huff_lds &t = T[lane];
@@ -183,10 +175,10 @@ __global__ __launch_bounds__(EN_LANES) void jpeg_decode_entropy_kernel(const uns
         }
     }
     for (int t = 0; t < n_tab; ++t)
-        for (int i = lane; i < 256; i += EN_LANES) T[t].vals[i] = spec[t * SET_TABLE + 16 + i];
+        for (int i = lane; i < 256; i += lanes) T[t].vals[i] = spec[t * SET_TABLE + 16 + i];
     __syncthreads();
     for (int t = 0; t < n_tab; ++t)
-        for (int e = lane; e < 256; e += EN_LANES) {
+        for (int e = lane; e < 256; e += lanes) {
             unsigned short hit = 0;
             for (int l = 8; l >= 1; --l) {  // (a valid specification is prefix-free: at most one length matches)
                 const int d = (e >> (8 - l)) - T[t].first[l];
@@ -195,6 +187,22 @@ __global__ __launch_bounds__(EN_LANES) void jpeg_decode_entropy_kernel(const uns
             T[t].lut[e] = hit;
         }
     __syncthreads();
+}
+
+// Units per workgroup.  A wave runs the distinct paths of its live lanes one after the other, so fewer lanes per wave buy less
+// serialisation at the price of more table builds: 16 was measured against 64 (MEASUREMENTS.md, "JPEG decode").
+constexpr int EN_LANES = 16;
+
+__global__ __launch_bounds__(EN_LANES) void jpeg_decode_entropy_kernel(const unsigned int *__restrict__ data, const int *__restrict__ meta,
+                                                                       const unsigned char *__restrict__ sets, short *__restrict__ coef,
+                                                                       const dec_geom g) {
+    __shared__ huff_lds T[6];
+    __shared__ unsigned char zig[64];
+    const int lane = threadIdx.x, f = blockIdx.y;
+    const int *unit_off = meta, *frame_unit = meta + g.n_units + 1, *frame_ri = frame_unit + g.F + 1, *frame_set = frame_ri + g.F;
+    const int set = min(max(frame_set[f], 0), g.n_sets - 1);
+    const unsigned char *spec = sets + (size_t)set * A3D_JPEG_TABSET_BYTES + SET_QUANT;
+    build_tables(T, zig, spec, 2 * g.ncomp, lane, EN_LANES);
 
     const int u0 = frame_unit[f], u1 = frame_unit[f + 1];
     const long long k = (long long)blockIdx.x * EN_LANES + lane;  // this lane's unit within the frame
@@ -226,6 +234,283 @@ __global__ __launch_bounds__(EN_LANES) void jpeg_decode_entropy_kernel(const uns
     }
     const int st = rd.ran_short() ? A3D_JPEG_SHORT : ok ? 0 : A3D_JPEG_BAD_CODE;
     if (st) atomicMax(reinterpret_cast<int *>(cf + g.cblk[3] * 64), st);
+}
+
+// ---- entropy, self-synchronising (a3d_jpeg_decode_split) --------------------------------------------------------------------------------
+// A unit's stuffed bytes are cut into subsequences of S = max(split_bytes, ceil(unit bytes / lpu)) bytes, one lane each; the lpu lanes
+// of a unit (a power of two, 1024 at the most) sit in one workgroup, and a workgroup holds blockDim / lpu units of one frame, so all
+// synchronisation is LDS and barriers.  A decoder state between two syntax elements is (position, slot within the MCU, zig-zag index;
+// 0: a DC symbol is next), one 64-bit word.  Round 0 walks lane j >= 1 from (its first data bit, 0, 0) and lane 0 from the unit's
+// start; in every later round a lane whose left neighbour's exit differs from the entry it last used walks again from there, until a
+// round changes nothing (a workgroup vote) or lpu rounds have run: after round r the lanes 0 .. r hold their true states, so the fixed
+// point is the sequential walk whatever the stream holds.  A speculative walk carries on past an inconsistency (it consumes what the
+// law consumes, ends the block, goes to the next slot) and records the number of blocks it had begun by then.  An exclusive sum of the
+// begun-block counts gives every lane the ordinal of its first block; the first flagged lane whose bad block is one of the unit's ends
+// the unit.  Then every lane in front of it walks once more from its true entry and stores AC values at their places and the DC
+// DIFFERENCE at coefficient 0, the unit's last lane walking on (zeros past the bytes) until the unit's blocks are done; a per-component
+// sum of the differences in scan order, modulo 2^16, turns them into DC values behind a barrier.
+//
+// What keeps every access inside the call's buffers: the reader fetches bytes of [lo, hi) of its unit only, both clamped to the data
+// (zeros beyond); a block's ordinal is tested against the unit's block count before its address is formed, so it lies in the unit's
+// own MCUs; a coefficient index is at most 63 by the tests of `element`; LDS is indexed by the thread and by its unit within the
+// workgroup.  Every loop is bounded: a walk by its end bit or by the unit's blocks (an element moves the index forward and a block
+// takes at most 64 of them), the rounds by lpu.
+constexpr int SP_LANES = 1024;     // threads of a workgroup, and lanes of a unit, at the most
+constexpr int SP_SATURATE = 1 << 30;  // above every unit's block count (201 M for 65535 x 65535 at 4:4:4)
+
+struct pos_reader {
+    const unsigned int *words;
+    unsigned long long acc;  // the low `cnt` bits are the stream's next bits
+    unsigned long long skp;  // beside acc: the last bit of a data byte FF that has a stuffed 00 behind it
+    long long bp;            // bits from the unit's first byte to the next unread bit, stuffed bytes counted: always on a data byte
+    unsigned int w;
+    int cnt, pos, end, widx;
+    bool ff;
+    __device__ __forceinline__ void refill() {
+        while (cnt <= 56) {
+            unsigned int b = 0;
+            for (;;) {
+                if (pos >= end) {  // past the unit: zeros
+                    b = 0, ff = false;
+                    break;
+                }
+                const int wi = pos >> 2;
+                if (wi != widx) widx = wi, w = words[wi];
+                b = (w >> (8 * (pos & 3))) & 0xFFu;
+                ++pos;
+                if (ff && b == 0) {  // FF 00 is the data byte FF: the FF is the newest byte in acc, whose last bit is never taken
+                    ff = false;      // before the next refill (an element takes at most 31 of the 32 bits a refill leaves)
+                    skp |= 1ull;
+                    continue;
+                }
+                ff = b == 0xFFu;
+                break;
+            }
+            acc = acc << 8 | b;
+            skp <<= 8;
+            cnt += 8;
+        }
+    }
+    // At bit `at` of the unit [lo, hi) of the data; `at` rests on a data byte (or lies past the unit).
+    __device__ __forceinline__ void start(const unsigned int *data, const int lo, const int hi, const long long at) {
+        words = data, acc = 0, skp = 0, w = 0, cnt = 0, widx = -1, ff = false, bp = at, end = hi;
+        pos = (at >> 3) < (long long)(hi - lo) ? lo + (int)(at >> 3) : hi;
+        refill();
+        cnt -= (int)(at & 7);
+    }
+    __device__ __forceinline__ void take(const int n) {  // 1 <= n <= 16 <= cnt
+        const unsigned int m = (unsigned int)(skp >> (cnt - n)) & ((1u << n) - 1u);
+        bp += n + 8 * __popc(m);
+        cnt -= n;
+    }
+    // As bit_reader::symbol: the next symbol of table t, or -1 where the next 16 bits start no code (they are consumed).
+    __device__ __forceinline__ int symbol(const huff_lds &t) {
+        if (cnt < 32) refill();
+        const unsigned int p = (unsigned int)(acc >> (cnt - 16)) & 0xFFFFu;
+        const unsigned int e = t.lut[p >> 8];
+        if (e) {
+            take((int)(e >> 8));
+            return (int)(e & 255u);
+        }
+        for (int l = 9; l <= 16; ++l) {
+            const int d = (int)(p >> (16 - l)) - t.first[l];
+            if (d >= 0 && d < (int)t.nb[l]) {
+                take(l);
+                return t.vals[min(t.cum[l - 1] + d, 255)];
+            }
+        }
+        take(16);
+        return -1;
+    }
+    __device__ __forceinline__ int value(const int s) {  // s <= 15 bits behind a symbol, extended
+        if (s == 0) return 0;
+        const int v = (int)(acc >> (cnt - s)) & ((1 << s) - 1);
+        take(s);
+        return v >> (s - 1) ? v : v - (1 << s) + 1;
+    }
+};
+
+// One element at zig-zag index idx of a block whose tables are dc / ac; false at an inconsistency (idx is then left as it was).
+// k >= 0: coefficient k (zig-zag) has the value val, the DC difference for k = 0.  idx = 64: the block is done.
+__device__ __forceinline__ bool element(pos_reader &rd, const huff_lds &dc, const huff_lds &ac, int &idx, int &k, int &val) {
+    k = -1;
+    if (idx == 0) {
+        const int s = rd.symbol(dc);
+        if (s < 0 || s > 15) return false;
+        k = 0, val = rd.value(s), idx = 1;
+        return true;
+    }
+    const int rs = rd.symbol(ac);
+    if (rs < 0) return false;
+    const int r = rs >> 4, sz = rs & 15;
+    if (sz == 0) {
+        if (r != 15) {  // EOB
+            idx = 64;
+            return true;
+        }
+        if (idx + 16 > 64) return false;
+        idx += 16;  // ZRL
+        return true;
+    }
+    if (idx + r > 63) return false;
+    k = idx + r, val = rd.value(sz), idx = k + 1;
+    return true;
+}
+
+__device__ __forceinline__ unsigned long long pack_state(const long long bp, const int slot, const int idx) {
+    return (unsigned long long)bp << 9 | (unsigned int)(slot << 6 | idx);
+}
+
+// Inclusive sum over the lpu lanes of a unit (lpu a power of two, segments aligned to it), through s[blockDim]; SAT: saturating at
+// SP_SATURATE (the operands are not negative), else modulo 2^32.  Every thread of the workgroup calls it; it ends behind a barrier.
+template <bool SAT>
+__device__ __forceinline__ unsigned int unit_inclusive_scan(const unsigned int v, unsigned int *s, const int jl, const int lpu) {
+    const int t = threadIdx.x;
+    s[t] = v;
+    __syncthreads();
+    for (int d = 1; d < lpu; d <<= 1) {
+        const unsigned int u = jl >= d ? s[t - d] : 0u;
+        __syncthreads();
+        s[t] = SAT ? min(s[t] + u, (unsigned int)SP_SATURATE) : s[t] + u;
+        __syncthreads();
+    }
+    return s[t];
+}
+
+__global__ __launch_bounds__(SP_LANES) void jpeg_decode_split_kernel(const unsigned int *__restrict__ data, const int *__restrict__ meta,
+                                                                     const unsigned char *__restrict__ sets, short *__restrict__ coef, const dec_geom g,
+                                                                     const int split, const int lpu) {
+    __shared__ huff_lds T[6];
+    __shared__ unsigned char zig[64];
+    __shared__ unsigned long long s_exit[SP_LANES];
+    __shared__ unsigned int s_scan[SP_LANES];
+    __shared__ int s_bad[SP_LANES], s_lim[SP_LANES];  // per unit of the workgroup: its first flagged lane; the blocks its DC sums cover
+    const int t = threadIdx.x, f = blockIdx.y;
+    const int *unit_off = meta, *frame_unit = meta + g.n_units + 1, *frame_ri = frame_unit + g.F + 1, *frame_set = frame_ri + g.F;
+    const int set = min(max(frame_set[f], 0), g.n_sets - 1);
+    build_tables(T, zig, sets + (size_t)set * A3D_JPEG_TABSET_BYTES + SET_QUANT, 2 * g.ncomp, t, (int)blockDim.x);
+
+    const int ul = t / lpu, jl = t - ul * lpu;  // the unit within the workgroup, the lane within the unit
+    const int u0 = frame_unit[f], u1 = frame_unit[f + 1];
+    const long long k = (long long)blockIdx.x * ((int)blockDim.x / lpu) + ul;  // the unit within the frame
+    const long long total = (long long)g.mx * g.my;
+    const long long ri = frame_ri[f] > 0 ? frame_ri[f] : total;
+    const long long m0 = k * ri;
+    const bool unit_ok = u0 >= 0 && u1 <= g.n_units && k < (long long)u1 - u0 && m0 < total;
+    const int hv = g.hs * g.vs, nslot = g.ncomp == 1 ? 1 : hv + 2;
+    const int n_blocks = unit_ok ? (int)((min(m0 + ri, total) - m0) * nslot) : 0;
+    int lo = 0, len = 0;
+    if (unit_ok) {
+        const int u = u0 + (int)k;
+        lo = min(max(unit_off[u], 0), g.data_bytes);
+        len = min(max(unit_off[u + 1], lo), g.data_bytes) - lo;
+    }
+    const int S = max(max(split, (len + lpu - 1) / lpu), 1);
+    const int n_sub = max((len + S - 1) / S, 1);
+    const bool active = unit_ok && jl < n_sub, last = jl == n_sub - 1;
+    const long long end_bit = 8 * min((long long)(jl + 1) * S, (long long)len);
+    short *cf = coef + (size_t)f * g.coef_frame;
+
+    // ---- the rounds ----
+    unsigned long long entry = 0, exit_state = 0;
+    int begun = 0, bad_at = -1;
+    if (active && jl > 0) {
+        long long q = (long long)jl * S;  // < len
+        const int i = lo + (int)q;
+        const unsigned int b0 = (data[i >> 2] >> (8 * (i & 3))) & 0xFFu, b1 = (data[(i - 1) >> 2] >> (8 * ((i - 1) & 3))) & 0xFFu;
+        if (b0 == 0 && b1 == 0xFFu) ++q;  // the 00 behind an FF is no data
+        entry = pack_state(8 * q, 0, 0);
+    }
+    if (jl == 0) s_bad[ul] = 0x7FFFFFFF, s_lim[ul] = n_blocks;
+    bool need = active;
+    for (int r = 0;; ++r) {
+        if (need) {
+            pos_reader rd;
+            rd.start(data, lo, lo + len, (long long)(entry >> 9));
+            int slot = (int)(entry >> 6) & 7, idx = (int)entry & 63;
+            begun = 0, bad_at = -1;
+            while (rd.bp < end_bit) {
+                const int c = slot < hv ? 0 : slot - hv + 1;
+                if (idx == 0) ++begun;
+                int kk, val;
+                if (!element(rd, T[2 * c], T[2 * c + 1], idx, kk, val)) {
+                    if (bad_at < 0) bad_at = begun;
+                    idx = 64;
+                }
+                if (idx == 64) idx = 0, slot = slot + 1 == nslot ? 0 : slot + 1;
+            }
+            exit_state = pack_state(rd.bp, slot, idx);
+        }
+        __syncthreads();  // every lane has read its neighbour's exit of the round before
+        if (need) s_exit[t] = exit_state;
+        const int any = __syncthreads_or(need);
+        if ((r > 0 && !any) || r + 1 >= lpu) break;
+        need = false;
+        if (active && jl > 0 && s_exit[t - 1] != entry) entry = s_exit[t - 1], need = true;
+    }
+
+    // ---- positions, and where the unit ends ----
+    const int prefix = (int)unit_inclusive_scan<true>(active ? (unsigned int)begun : 0u, s_scan, jl, lpu) - (active ? min(begun, SP_SATURATE) : 0);
+    if (active && bad_at >= 0 && (long long)prefix + bad_at - 1 < n_blocks) atomicMin(&s_bad[ul], jl);
+    __syncthreads();
+
+    // ---- the write pass ----
+    if (active && prefix <= n_blocks && jl <= s_bad[ul]) {
+        pos_reader rd;
+        rd.start(data, lo, lo + len, (long long)(entry >> 9));
+        int slot = (int)(entry >> 6) & 7, idx = (int)entry & 63;
+        int n = 0, st = 0;  // blocks begun here
+        short *dst = nullptr;
+        auto block_at = [&](const int ordinal, const int sl) -> short * {
+            const long long m = m0 + ordinal / nslot;
+            const int mxi = (int)(m % g.mx), myi = (int)(m / g.mx);
+            const int c = sl < hv ? 0 : sl - hv + 1, vy = c == 0 ? sl / g.hs : 0, vx = c == 0 ? sl - vy * g.hs : 0;
+            return cf + (g.cblk[c] + (long long)(myi * g.v[c] + vy) * g.bw[c] + mxi * g.h[c] + vx) * 64;
+        };
+        if (idx > 0 && prefix > 0) dst = block_at(prefix - 1, slot);
+        for (;;) {
+            if (idx == 0 && prefix + n >= n_blocks) {  // the unit's blocks are done
+                if (rd.bp > 8ll * len) st = A3D_JPEG_SHORT;
+                break;
+            }
+            if (!last && rd.bp >= end_bit) break;
+            if (idx == 0) dst = block_at(prefix + n, slot), ++n;
+            const int c = slot < hv ? 0 : slot - hv + 1;
+            const bool was_dc = idx == 0;
+            int kk, val;
+            if (!element(rd, T[2 * c], T[2 * c + 1], idx, kk, val)) {  // the unit's first inconsistency: the law ends the unit here
+                st = rd.bp > 8ll * len ? A3D_JPEG_SHORT : A3D_JPEG_BAD_CODE;
+                s_lim[ul] = prefix + n - (was_dc ? 1 : 0);  // the law keeps the DC value of a block whose DC symbol was sound
+                break;
+            }
+            if (kk >= 0 && val != 0 && dst) dst[zig[kk]] = (short)val;
+            if (idx == 64) idx = 0, slot = slot + 1 == nslot ? 0 : slot + 1;
+        }
+        if (st) atomicMax(reinterpret_cast<int *>(cf + g.cblk[3] * 64), st);
+    }
+    __syncthreads();  // the differences are in memory, s_lim is final
+
+    // ---- the DC pass ----
+    const int lim = unit_ok ? min(max(s_lim[ul], 0), n_blocks) : 0;
+    for (int c = 0; c < g.ncomp; ++c) {
+        const int hvc = g.h[c] * g.v[c], sb = c == 0 ? 0 : hv + c - 1;
+        const long long n_c = (long long)(lim / nslot) * hvc + min(max(lim % nslot - sb, 0), hvc);  // the component's blocks in front of `lim`
+        const long long per = (n_c + lpu - 1) / lpu, q0 = min(jl * per, n_c), q1 = min(q0 + per, n_c);
+        auto dc_at = [&](const long long q) -> short * {
+            const long long m = m0 + q / hvc;
+            const int wi = (int)(q % hvc), vy = wi / g.h[c], vx = wi - vy * g.h[c];
+            const int mxi = (int)(m % g.mx), myi = (int)(m / g.mx);
+            return cf + (g.cblk[c] + (long long)(myi * g.v[c] + vy) * g.bw[c] + mxi * g.h[c] + vx) * 64;
+        };
+        unsigned int sum = 0;
+        for (long long q = q0; q < q1; ++q) sum += (unsigned int)(int)*dc_at(q);
+        unsigned int run = unit_inclusive_scan<false>(sum, s_scan, jl, lpu) - sum;
+        for (long long q = q0; q < q1; ++q) {
+            short *p = dc_at(q);
+            run += (unsigned int)(int)*p;
+            *p = (short)run;
+        }
+    }
 }
 
 // ---- dequantise + IDCT ----------------------------------------------------------------------------------------------------------------
@@ -375,7 +660,8 @@ extern "C" int a3d_jpeg_decode_scratch(int H, int W, int ncomp, int hs, int vs, 
     return A3D_OK;
 }
 
-extern "C" int a3d_jpeg_decode(const a3d_jpeg_decode_desc *d, void *stream) {
+// Both entry points: split_bytes = 0 is a3d_jpeg_decode's one lane per unit, above it a3d_jpeg_decode_split's entropy launch.
+static int decode_launch(const a3d_jpeg_decode_desc *d, const int split_bytes, void *stream) {
     dec_geom g;
     if (!d || !make_geom(d->F, d->H, d->W, d->pitch, d->ncomp, d->hs, d->vs, &g)) return A3D_ERR_ARG;
     if (d->F == 0) return A3D_OK;
@@ -385,8 +671,11 @@ extern "C" int a3d_jpeg_decode(const a3d_jpeg_decode_desc *d, void *stream) {
         return A3D_ERR_ARG;
     if ((uintptr_t)d->d_data % 4 || (uintptr_t)d->d_sets % 8 || (uintptr_t)d->coef % 16 || (uintptr_t)d->planes % 8) return A3D_ERR_ARG;
     if (d->unit_off[0] != 0 || d->unit_off[d->n_units] != d->data_bytes || d->frame_unit[0] != 0 || d->frame_unit[d->F] != d->n_units) return A3D_ERR_ARG;
-    for (int u = 0; u < d->n_units; ++u)
+    int longest = 0;
+    for (int u = 0; u < d->n_units; ++u) {
         if (d->unit_off[u + 1] < d->unit_off[u]) return A3D_ERR_ARG;
+        longest = d->unit_off[u + 1] - d->unit_off[u] > longest ? d->unit_off[u + 1] - d->unit_off[u] : longest;
+    }
     const long long total = (long long)g.mx * g.my;
     long long most = 0;
     for (int f = 0; f < d->F; ++f) {
@@ -408,16 +697,35 @@ extern "C" int a3d_jpeg_decode(const a3d_jpeg_decode_desc *d, void *stream) {
     g.n_units = d->n_units, g.n_sets = d->n_sets, g.data_bytes = (int)d->data_bytes;
     const long long n_blocks = (long long)d->F * g.cblk[3], id_grid = (n_blocks + ID_BLOCKS - 1) / ID_BLOCKS;
     const int groups = (d->W + 15) / 16;
-    const long long n_groups = (long long)d->F * d->H * groups, co_grid = (n_groups + 255) / 256, en_grid = (most + EN_LANES - 1) / EN_LANES;
+    const long long n_groups = (long long)d->F * d->H * groups, co_grid = (n_groups + 255) / 256;
+    // split: the lanes of a unit are the power of two that gives the longest unit of the call subsequences of split_bytes, and a
+    // workgroup is as many units of `lpu` lanes as the frame with the most units fills, 1024 threads at the most.
+    int lpu = 1, threads = EN_LANES;
+    if (split_bytes > 0) {
+        while (lpu < SP_LANES && (long long)lpu * split_bytes < longest) lpu *= 2;
+        const long long step = lpu > 64 ? lpu : 64, want = (most * lpu + step - 1) / step * step;
+        threads = (int)(want < SP_LANES ? want : SP_LANES);
+    }
+    const long long per_group = threads / lpu, en_grid = (most + per_group - 1) / per_group;
     if (id_grid > 0x7FFFFFFFll || co_grid > 0x7FFFFFFFll || en_grid > 0x7FFFFFFFll) return A3D_ERR_ARG;
     const int vec = (uintptr_t)d->rgb % 16 == 0 && ((size_t)d->pitch * 3) % 16 == 0;
     a3d_begin();
     if (hipMemsetAsync(d->coef, 0, (size_t)d->F * g.coef_frame * sizeof(short), (hipStream_t)stream) != hipSuccess) return A3D_ERR_LAUNCH;
-    hipLaunchKernelGGL(jpeg_decode_entropy_kernel, dim3((unsigned int)en_grid, (unsigned int)d->F), dim3(EN_LANES), 0, (hipStream_t)stream,
-                       reinterpret_cast<const unsigned int *>(d->d_data), d->d_meta, d->d_sets, d->coef, g);
+    if (split_bytes > 0)
+        hipLaunchKernelGGL(jpeg_decode_split_kernel, dim3((unsigned int)en_grid, (unsigned int)d->F), dim3(threads), 0, (hipStream_t)stream,
+                           reinterpret_cast<const unsigned int *>(d->d_data), d->d_meta, d->d_sets, d->coef, g, split_bytes, lpu);
+    else
+        hipLaunchKernelGGL(jpeg_decode_entropy_kernel, dim3((unsigned int)en_grid, (unsigned int)d->F), dim3(EN_LANES), 0, (hipStream_t)stream,
+                           reinterpret_cast<const unsigned int *>(d->d_data), d->d_meta, d->d_sets, d->coef, g);
     hipLaunchKernelGGL(jpeg_decode_idct_kernel, dim3((unsigned int)id_grid), dim3(256), 0, (hipStream_t)stream, d->coef, d->d_meta, d->d_sets, d->planes,
                        g, n_blocks);
     hipLaunchKernelGGL(jpeg_decode_colour_kernel, dim3((unsigned int)co_grid), dim3(256), 0, (hipStream_t)stream, d->planes, d->coef, d->rgb, d->status, g,
                        n_groups, groups, vec);
     return a3d_check_launch();
+}
+
+extern "C" int a3d_jpeg_decode(const a3d_jpeg_decode_desc *d, void *stream) { return decode_launch(d, 0, stream); }
+
+extern "C" int a3d_jpeg_decode_split(const a3d_jpeg_decode_desc *d, int split_bytes, void *stream) {
+    return split_bytes < 1 ? A3D_ERR_ARG : decode_launch(d, split_bytes, stream);
 }

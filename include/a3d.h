@@ -1247,6 +1247,26 @@ typedef struct {
  * at data_bytes / n_units, a frame whose unit count is not ceil(mx my / interval), a table index out of range, a Huffman
  * specification whose codes do not fit their lengths, or data_bytes above 2^31 - 1.  F == 0 is a no-op. */
 int a3d_jpeg_decode(const a3d_jpeg_decode_desc *d, void *stream);
+/* a3d_jpeg_decode with a self-synchronising entropy launch: a unit (above all a scan without restart intervals) is decoded by many
+ * lanes at once.  The same descriptor, scratch, validation, A3D_ERR_ARG cases and status codes; split_bytes < 1 is A3D_ERR_ARG as well.
+ * The law: for every input status[f] is what a3d_jpeg_decode gives, and every frame whose status is 0 has the same RGB bytes (of a
+ * frame with another status nothing is asked, as above).  No stream content can make a read or a write leave the buffers of the call,
+ * and a unit writes only its own blocks.  The result does not depend on split_bytes, on F or on the frames beside a frame: it is
+ * exact by construction, never by a stream happening to synchronise.
+ *   scheme    a unit's stuffed bytes are cut into subsequences of S = max(split_bytes, ceil(unit bytes / L)) bytes, one lane each; the
+ *             L <= 1024 lanes of a unit share a workgroup (short units share one), so nothing synchronises across workgroups.  A
+ *             decoder state between two syntax elements is (bit position, block slot within the MCU, zig-zag index; 0 = a DC symbol
+ *             is next).  Round 0 walks every subsequence from (its first bit, slot 0, index 0), the first from the unit's start; in
+ *             each later round a lane takes its left neighbour's exit state as its entry and walks again if that differs from the
+ *             entry it last used, until a round changes nothing or as many rounds as subsequences have run: after round r the lanes
+ *             0 .. r hold their true states, so the fixed point is the sequential walk.  A speculative walk carries on past an
+ *             inconsistency (it consumes what the law consumes, ends the block, goes to the next slot); the rule affects the number
+ *             of rounds only.  A prefix sum of the blocks each lane began places its blocks; the first inconsistency of the true chain
+ *             inside the unit's blocks ends the unit as in the law, and the last lane reads zeros past the unit until its blocks are
+ *             done (SHORT over BAD_CODE, the cause).  A second walk from the true entries stores AC values and DC differences, and a
+ *             sum per unit and component, modulo 2^16, turns the differences into DC values.
+ * The memset, the dequantise + IDCT launch and the upsample + colour launch are a3d_jpeg_decode's own. */
+int a3d_jpeg_decode_split(const a3d_jpeg_decode_desc *d, int split_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,8 @@
 """Measures the JPEG decode path end to end, from file bytes in host memory to uint8 RGB on the device, against what the package did
 before it had a decoder: PIL on one host thread plus the upload.
 
-    python tools/decode_bench.py [--frames 90] [--repeats 3] [--chunks 8,32] [--kernels]
+    python tools/decode_bench.py [--frames 90] [--repeats 3] [--chunks 8,32] [--kernels] [--splits 32,64,128,256]
+    python tools/decode_bench.py --rounds [--splits 32,64,128,256]      (no GPU: the host model's convergence figures)
 
 Three classes of stream (MEASUREMENTS.md, "JPEG decode"):
   (a) the package's own files, video.jpeg_encode at quality 90: 480 x 2560 visualisation rows and 480 x 640 frames (4:4:4, one MCU row
@@ -10,8 +11,12 @@ Three classes of stream (MEASUREMENTS.md, "JPEG decode"):
   (b) PIL 480 x 640 quality-90 4:2:0 files without restart intervals;
   (c) the same with restart_marker_rows=1.
 Per class and chunk: frames/s of video.jpeg_decode (parse + upload + kernels, synchronised at the end), `--repeats` times; frames/s of
-PIL + upload, as often; the bytes that cross PCIe and the bytes the kernels move.  `--kernels` adds the device time of every launch of
-one call, from torch.profiler's kernel records.  One JSON object per line."""
+PIL + upload, as often; the bytes that cross PCIe and the bytes the kernels move; then the same call with entropy="split" (the
+entropy launch that cuts a unit into subsequences which synchronise themselves) at the default subsequence size, and at every size of
+`--splits` for the largest chunk.  `--kernels` adds the device time of every launch of one call, from torch.profiler's kernel records.
+`--rounds` runs nowhere near a GPU: per class it prints the subsequences and the synchronisation rounds of the longest unit of the
+first file under tests/jpeg_split_ref.py, the scheme's host model (class (a) is then written by tests/mjpeg_ref.py, the encoder's law,
+whose bytes are the package's own).  One JSON object per line."""
 from __future__ import annotations
 
 import argparse
@@ -54,23 +59,28 @@ def pil_files(frames, **options):
     return out
 
 
-def classes(n):
-    from articulation3d_amd import video
-
+def classes(n, host_only=False):
     base = smooth_frames(min(n, 6), 480, 640)
     frames = base[np.arange(n) % len(base)]
-    own = video.jpeg_encode(torch.from_numpy(base).cuda(), 90)
-    rows = video.jpeg_encode(torch.from_numpy(np.concatenate([base[:3]] * 4, 2)).cuda(), 90)
+    if host_only:
+        import mjpeg_ref
+
+        own, rows = [mjpeg_ref.encode_frame(base[0], 90)], [mjpeg_ref.encode_frame(np.concatenate([base[0]] * 4, 1), 90)]
+    else:
+        from articulation3d_amd import video
+
+        own = video.jpeg_encode(torch.from_numpy(base).cuda(), 90)
+        rows = video.jpeg_encode(torch.from_numpy(np.concatenate([base[:3]] * 4, 2)).cuda(), 90)
     return {"a_rows_480x2560": [rows[k % len(rows)] for k in range(n)], "a_frames_480x640": [own[k % len(own)] for k in range(n)],
             "b_pil_420_no_restart": pil_files(frames), "c_pil_420_restart_rows": pil_files(frames, restart_marker_rows=1)}
 
 
-def time_gpu(jpegs, chunk):
+def time_gpu(jpegs, chunk, **how):
     from articulation3d_amd import video
 
     torch.cuda.synchronize()
     t = time.perf_counter()
-    out = video.jpeg_decode(jpegs, chunk=chunk)
+    out = video.jpeg_decode(jpegs, chunk=chunk, **how)
     torch.cuda.synchronize()
     return len(jpegs) / (time.perf_counter() - t), out
 
@@ -86,14 +96,14 @@ def time_pil(jpegs):
     return len(jpegs) / (time.perf_counter() - t), out
 
 
-def kernel_times(jpegs, chunk):
-    """Device time per launch of the first a3d_jpeg_decode call of a run, from torch.profiler: {kernel name: microseconds}."""
+def kernel_times(jpegs, chunk, **how):
+    """Device time per launch of the first a3d_jpeg_decode (or _split) call of a run, from torch.profiler: {kernel name: microseconds}."""
     from torch.profiler import ProfilerActivity, profile
 
     from articulation3d_amd import video
 
     with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        video.jpeg_decode(jpegs[:chunk], chunk=chunk)
+        video.jpeg_decode(jpegs[:chunk], chunk=chunk, **how)
         torch.cuda.synchronize()
     out = {}
     for e in prof.events():
@@ -103,13 +113,34 @@ def kernel_times(jpegs, chunk):
     return out
 
 
+def rounds(splits):
+    """Per class the longest unit of the first file: its bytes and, per subsequence size, (subsequences, rounds) of the host model."""
+    import jpeg_decode_ref
+    import jpeg_split_ref
+
+    for name, jpegs in classes(1, host_only=True).items():
+        p = jpeg_decode_ref.parse(jpegs[0])
+        scan = jpeg_split_ref.Scan(p)
+        unit = jpeg_split_ref.Unit(max(scan.units, key=len))
+        row = {"class": name, "units_per_frame": scan.n_units, "longest_unit_bytes": unit.n}
+        for split in splits:
+            n_rounds, subs = jpeg_split_ref.synchronise(scan, unit, split)
+            row[f"split{split}"] = {"bytes": jpeg_split_ref.split_size(unit.n, split), "subsequences": len(subs), "rounds": n_rounds}
+        print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--frames", default=90, type=int)
     ap.add_argument("--repeats", default=3, type=int)
     ap.add_argument("--chunks", default="8,32")
     ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--splits", default="32,64,128,256", help="subsequence sizes of the split path to sweep at the largest chunk")
+    ap.add_argument("--rounds", action="store_true", help="no GPU: subsequences and rounds per class from the host model")
     args = ap.parse_args()
+    splits = [int(v) for v in args.splits.split(",")]
+    if args.rounds:
+        return rounds(splits)
     from articulation3d_amd import opt_ops, video
 
     for name, jpegs in classes(args.frames).items():
@@ -125,15 +156,28 @@ def main():
                # per frame: uploaded scan bytes; memset + coefficient writes and reads (int16), planes written and read, RGB written
                "bytes_per_frame": {"h2d": round(scan), "coef_memset": 2 * ce, "coef_read": 2 * ce, "planes_write_read": 2 * pe, "rgb_write": rgb,
                                    "pil_path_h2d": rgb}}
-        for chunk in (int(c) for c in args.chunks.split(",")):
-            runs = [time_gpu(jpegs, chunk) for _ in range(args.repeats)]
-            assert torch.equal(runs[0][1][:4], want), "the GPU decoder and PIL disagree"
-            row[f"gpu_fps_chunk{chunk}"] = [round(r[0], 1) for r in runs]
+        chunks = [int(c) for c in args.chunks.split(",")]
+        time_gpu(jpegs[:4], 4, entropy="split")
+        for chunk in chunks:
+            for key, how in (("gpu", {}), ("split", {"entropy": "split"})):
+                runs = [time_gpu(jpegs, chunk, **how) for _ in range(args.repeats)]
+                assert torch.equal(runs[0][1][:4], want), f"the GPU decoder ({key}) and PIL disagree"
+                row[f"{key}_fps_chunk{chunk}"] = [round(r[0], 1) for r in runs]
+                if args.kernels:
+                    try:
+                        row[f"{key}_kernel_us_chunk{chunk}"] = kernel_times(jpegs, chunk, **how)
+                    except Exception as e:  # a profiler that is not there is not a failed measurement
+                        row[f"{key}_kernel_us_chunk{chunk}"] = f"unavailable: {type(e).__name__}: {e}"
+        for split in splits:  # the sweep the default subsequence size is taken from, at the largest chunk
+            how = {"entropy": "split", "split_bytes": split}
+            runs = [time_gpu(jpegs, max(chunks), **how) for _ in range(args.repeats)]
+            assert torch.equal(runs[0][1][:4], want), f"the GPU decoder (split {split}) and PIL disagree"
+            row[f"split{split}_fps_chunk{max(chunks)}"] = [round(r[0], 1) for r in runs]
             if args.kernels:
                 try:
-                    row[f"kernel_us_chunk{chunk}"] = kernel_times(jpegs, chunk)
-                except Exception as e:  # a profiler that is not there is not a failed measurement
-                    row[f"kernel_us_chunk{chunk}"] = f"unavailable: {type(e).__name__}: {e}"
+                    row[f"split{split}_kernel_us_chunk{max(chunks)}"] = kernel_times(jpegs, max(chunks), **how).get("jpeg_decode_split_kernel")
+                except Exception as e:
+                    row[f"split{split}_kernel_us_chunk{max(chunks)}"] = f"unavailable: {type(e).__name__}: {e}"
         print(json.dumps(row), flush=True)
 
 

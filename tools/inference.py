@@ -15,7 +15,8 @@ Input (this image has no H.264 decoder: cv2 / imageio are absent, so .mp4 / .mov
     container's rate, or
   * a directory of .png / .jpg frames, sorted by name: baseline JPEG files of one size go through the same GPU decoder, everything
     else (PNG, progressive or otherwise refused files, frames the decoder flags) through PIL -- `--decoder auto|gpu|pil`, the frames
-    are the same bytes under all three, or
+    are the same bytes under all three: `gpu` and `auto` send every baseline stream to the GPU, with restart intervals or without
+    (a scan without them is split among many lanes that synchronise themselves: jpeg_decode's entropy="split"), `pil` none, or
   * `synthetic:N` / `synthetic:NxHxW` -- N seeded random frames (plumbing check), optionally at a source size H x W.
 The frames go to the GPU as they come from the reader (uint8 RGB, any size): the reference's `cv2.resize(im, (640, 480))` and
 BGR flip (:216-218) run on the device, fused with the normalisation in front of the stem (a3d_preprocess_resize_u8).
@@ -66,9 +67,9 @@ def count_frames(path: str) -> int:
 
 def gpu_decodes(info, decoder: str) -> bool:
     """Whether a stream that jpeg_parse accepts goes to the GPU.  `gpu`: always.  `auto`: the classes that MEASUREMENTS.md ("JPEG decode")
-    found faster there than PIL on one host thread -- streams with restart intervals; a scan without them is one sequential
-    Huffman walk, which one GPU lane does more slowly than one CPU core."""
-    return decoder == "gpu" or (decoder == "auto" and info.restart > 0)
+    found faster there than PIL on one host thread -- since the entropy launch that splits a unit among many lanes, every class:
+    streams with restart intervals, and scans without them (nine times PIL's rate at 32 frames per call)."""
+    return decoder in ("gpu", "auto")
 
 
 def decode_images(blobs, decoder: str = "auto") -> np.ndarray:
@@ -94,8 +95,8 @@ def decode_images(blobs, decoder: str = "auto") -> np.ndarray:
             if gpu_decodes(info, decoder) and geometry in (None, info.geometry):
                 geometry = info.geometry
                 chosen.append(k)
-        if chosen:
-            out, status = jpeg_decode([blobs[k] for k in chosen], chunk=32, strict=False)
+        if chosen:  # the entropy launch that splits a unit among lanes: the same bytes, faster with and without restart intervals (MEASUREMENTS.md)
+            out, status = jpeg_decode([blobs[k] for k in chosen], chunk=32, strict=False, entropy="split")
             out = out.cpu().numpy()
             for i, k in enumerate(chosen):
                 if int(status[i]) == 0:
@@ -267,7 +268,7 @@ def build_parser() -> argparse.ArgumentParser:
                     help="--vis avi: frames per second, an integer or a ratio such as 30000/1001 (default: the rate of an .avi input, else 30)")
     ap.add_argument("--decoder", choices=("auto", "gpu", "pil"), default="auto",
                     help="who decodes JPEG input (.avi chunks, .jpg files): gpu = every baseline stream on the GPU, pil = PIL on the host, auto = "
-                         "the GPU for the streams it was measured to decode faster (those with restart intervals); the frames are the same bytes")
+                         "the GPU for the streams it was measured to decode faster (every baseline stream, with restart intervals or without); the frames are the same bytes")
     ap.add_argument("--mask-alpha", default=0.0, type=float,
                     help="--vis: opacity of the instance masks on the seg panels (0 = none, as the reference draws them)")
     ap.add_argument("--save-obj", action="store_true",
