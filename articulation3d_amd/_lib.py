@@ -288,7 +288,7 @@ class MeshDesc(C.Structure):
 
 
 JPEG_BLOCK_BITS, JPEG_HUFF_VALS = 1658, 162
-JPEG_RANGE, JPEG_BAD_CODE, JPEG_SHORT, JPEG_TABSET_BYTES = 1, 2, 3, 192 + 6 * (16 + 256)
+JPEG_RANGE, JPEG_BAD_CODE, JPEG_SHORT, JPEG_TABSET_BYTES, JPEG_SPLIT_BYTES = 1, 2, 3, 192 + 6 * (16 + 256), 32
 
 
 class JpegDecodeDesc(C.Structure):

@@ -2,24 +2,21 @@
 // uint8 [F,H,pitch,3] RGB, byte for byte what tests/jpeg_decode_ref.py computes.  Integer arithmetic only.  One memset (the
 // coefficient scratch, each frame's status word at its tail included) and three launches:
 //
-//   entropy   one lane per unit (a restart interval, or the whole scan), 16 units per workgroup, the lanes of a workgroup in one frame.
-//             The workgroup turns its frame's six Huffman specifications into an 8-bit lookahead table plus the Annex F first-code /
-//             count rows for the longer codes, in LDS.  A lane reads its unit by aligned dword loads, one cached word at a time, drops
-//             the 00 behind every FF, and writes each non-zero coefficient as int16 at its natural place in the zeroed scratch.  The
-//             lanes of a wave walk different streams, so their loops diverge, and a scan without restart intervals keeps one lane of
-//             one wave busy per frame: that is the price of the format, and MEASUREMENTS.md says what it costs.
-//             a3d_jpeg_decode_split launches jpeg_decode_split_kernel in its place: a unit is cut into subsequences that many lanes
-//             walk at once and that synchronise themselves ("entropy, self-synchronising" below); the other launches are the same.
+//   entropy   a unit (a restart interval, or the whole scan) is cut into subsequences that many lanes walk at once and that synchronise
+//             themselves; the lanes of a unit share a workgroup, short units share one, the units of a workgroup are of one frame
+//             ("entropy" below states the scheme).  The workgroup turns its frame's six Huffman specifications into an 8-bit
+//             lookahead table plus the Annex F first-code / count rows for the longer codes, in LDS.  A lane reads its bytes by
+//             aligned dword loads, one cached word at a time, drops the 00 behind every FF, and writes each non-zero coefficient as
+//             int16 at its natural place in the zeroed scratch.  The lanes of a wave walk different bytes, so their loops diverge:
+//             that is the price of the format, and MEASUREMENTS.md says what it costs.
 //   idct      32 blocks per workgroup, 8 lanes per block.  Lane r loads row r (one 16-byte load) and dequantises it, lane j transforms
 //             column j, lane r transforms row r and stores its 8 samples as one 8-byte word; rows meet columns in LDS (rows padded to 9
 //             words).  The domain test of the law is taken here and raised into the frame's status word.
 //   colour    one lane per 16 pixels of a row: chroma upsampled as the law states, converted, clamped, and stored as three 16-byte
 //             words where the destination allows (bytes otherwise).  The first lane of a frame publishes its status word.
 //
-// What keeps every access inside the call's buffers, whatever the stream holds: a lane's byte cursor runs over [lo, hi) of its unit,
-// both clamped to the data (past hi it reads zeros); a code's symbol index is below the table's symbol count by construction of the
-// first-code rows; a coefficient index is tested against 63 before the store; a unit's MCU range is clamped to the frame's MCUs, and
-// every block of an MCU inside that range lies inside the component's padded plane.
+// What keeps every access inside the call's buffers, whatever the stream holds, is stated with the entropy kernel; the dense launches
+// index by the geometry alone, and a frame's table index is clamped where it is read.
 #include "kernel_prims.h"
 #include "../../include/a3d.h"
 
@@ -40,6 +37,20 @@ struct dec_geom {
     long long cblk[4];               // first block of every component within a frame; cblk[ncomp] = blocks per frame
     long long coef_frame, plane_frame, poff[3];
     int n_units, n_sets, data_bytes;
+    // Block (vx, vy) of component c in MCU (mxi, myi), counted within a frame
+    __device__ __forceinline__ long long block(const int c, const int mxi, const int myi, const int vy, const int vx) const {
+        return cblk[c] + (long long)(myi * v[c] + vy) * bw[c] + mxi * h[c] + vx;
+    }
+};
+
+// d_meta: the descriptor's four host tables back to back.  The per-frame rows, and a frame's table set with its index clamped.
+struct dec_meta {
+    const int *unit_off, *frame_unit, *frame_ri, *frame_set;
+    __device__ __forceinline__ dec_meta(const int *meta, const dec_geom &g)
+        : unit_off(meta), frame_unit(meta + g.n_units + 1), frame_ri(frame_unit + g.F + 1), frame_set(frame_ri + g.F) {}
+    __device__ __forceinline__ const unsigned char *table_set(const unsigned char *sets, const dec_geom &g, const long long f) const {
+        return sets + (size_t)min(max(frame_set[f], 0), g.n_sets - 1) * A3D_JPEG_TABSET_BYTES;
+    }
 };
 
 bool make_geom(int F, int H, int W, int pitch, int ncomp, int hs, int vs, dec_geom *g) {
@@ -62,7 +73,7 @@ bool make_geom(int F, int H, int W, int pitch, int ncomp, int hs, int vs, dec_ge
     return true;
 }
 
-// ---- entropy ------------------------------------------------------------------------------------------------------------------------
+// ---- entropy: the tables ----------------------------------------------------------------------------------------------------------------
 struct huff_lds {
     unsigned short lut[256];  // 8 leading bits -> length << 8 | symbol of a code of at most 8 bits, else 0
     int first[17];            // first code of every length (Annex C)
@@ -70,91 +81,6 @@ struct huff_lds {
     unsigned short nb[17];    // codes of length l
     unsigned char vals[256];
 };
-
-struct bit_reader {
-    const unsigned int *words;
-    unsigned long long acc;  // the low `cnt` bits are the stream's next bits
-    unsigned int w;
-    int cnt, pos, end, widx, pad;
-    bool ff;
-    __device__ __forceinline__ void refill() {
-        while (cnt <= 56) {
-            unsigned int b;
-            for (;;) {
-                if (pos >= end) {  // past the unit: zeros, counted (8 or more of them in `acc` mean every bit there is one)
-                    b = 0, ff = false;
-                    pad = min(pad + 1, 16);
-                    break;
-                }
-                const int wi = pos >> 2;
-                if (wi != widx) widx = wi, w = words[wi];
-                b = (w >> (8 * (pos & 3))) & 0xFFu;
-                ++pos;
-                if (ff && b == 0) {  // FF 00 is the data byte FF
-                    ff = false;
-                    continue;
-                }
-                ff = b == 0xFFu;
-                break;
-            }
-            acc = acc << 8 | b;
-            cnt += 8;
-        }
-    }
-    // The next symbol of table t, or -1 where the next 16 bits start no code (they are consumed).  Leaves at least 16 bits in `acc`.
-    __device__ __forceinline__ int symbol(const huff_lds &t) {
-        if (cnt < 32) refill();
-        const unsigned int p = (unsigned int)(acc >> (cnt - 16)) & 0xFFFFu;
-        const unsigned int e = t.lut[p >> 8];
-        if (e) {
-            cnt -= (int)(e >> 8);
-            return (int)(e & 255u);
-        }
-        for (int l = 9; l <= 16; ++l) {
-            const int d = (int)(p >> (16 - l)) - t.first[l];
-            if (d >= 0 && d < (int)t.nb[l]) {
-                cnt -= l;
-                return t.vals[min(t.cum[l - 1] + d, 255)];
-            }
-        }
-        cnt -= 16;
-        return -1;
-    }
-    // s <= 15 bits behind a symbol, extended: the value of a coefficient of category s
-    __device__ __forceinline__ int value(const int s) {
-        if (s == 0) return 0;
-        const int v = (int)(acc >> (cnt - s)) & ((1 << s) - 1);
-        cnt -= s;
-        return v >> (s - 1) ? v : v - (1 << s) + 1;
-    }
-    __device__ __forceinline__ bool ran_short() const { return cnt < 8 * pad; }
-};
-
-// One block into its 64 zeroed coefficients; false at a bad code.
-__device__ __forceinline__ bool decode_block(bit_reader &rd, short *__restrict__ dst, int &pred, const huff_lds &dc, const huff_lds &ac,
-                                             const unsigned char *zig) {
-    const int s = rd.symbol(dc);
-    if (s < 0 || s > 15) return false;
-    pred = (short)(pred + rd.value(s));  // modulo 2^16
-    if (pred) dst[0] = (short)pred;
-    int i = 1;
-    while (i < 64) {
-        const int rs = rd.symbol(ac);
-        if (rs < 0) return false;
-        const int r = rs >> 4, sz = rs & 15;
-        if (sz == 0) {
-            if (r != 15) break;  // EOB
-            i += 16;             // ZRL
-            if (i > 64) return false;
-            continue;
-        }
-        i += r;
-        if (i > 63) return false;
-        dst[zig[i]] = (short)rd.value(sz);
-        ++i;
-    }
-    return true;
-}
 
 // The workgroup's form of a frame's Huffman specifications (`spec`: n_tab of them, bits[16] + vals[256] each) and the zig-zag order, in
 // LDS: every one of the workgroup's `lanes` threads calls it.  It ends behind a barrier.
@@ -189,54 +115,7 @@ __device__ __forceinline__ void build_tables(huff_lds *T, unsigned char *zig, co
     __syncthreads();
 }
 
-// Units per workgroup.  A wave runs the distinct paths of its live lanes one after the other, so fewer lanes per wave buy less
-// serialisation at the price of more table builds: 16 was measured against 64 (MEASUREMENTS.md, "JPEG decode").
-constexpr int EN_LANES = 16;
-
-__global__ __launch_bounds__(EN_LANES) void jpeg_decode_entropy_kernel(const unsigned int *__restrict__ data, const int *__restrict__ meta,
-                                                                       const unsigned char *__restrict__ sets, short *__restrict__ coef,
-                                                                       const dec_geom g) {
-    __shared__ huff_lds T[6];
-    __shared__ unsigned char zig[64];
-    const int lane = threadIdx.x, f = blockIdx.y;
-    const int *unit_off = meta, *frame_unit = meta + g.n_units + 1, *frame_ri = frame_unit + g.F + 1, *frame_set = frame_ri + g.F;
-    const int set = min(max(frame_set[f], 0), g.n_sets - 1);
-    const unsigned char *spec = sets + (size_t)set * A3D_JPEG_TABSET_BYTES + SET_QUANT;
-    build_tables(T, zig, spec, 2 * g.ncomp, lane, EN_LANES);
-
-    const int u0 = frame_unit[f], u1 = frame_unit[f + 1];
-    const long long k = (long long)blockIdx.x * EN_LANES + lane;  // this lane's unit within the frame
-    if (u0 < 0 || u1 > g.n_units || k >= (long long)u1 - u0) return;
-    const long long total = (long long)g.mx * g.my;
-    const long long ri = frame_ri[f] > 0 ? frame_ri[f] : total;
-    const long long m0 = k * ri, m1 = min(m0 + ri, total);
-    if (m0 >= total) return;
-    const int u = u0 + (int)k;
-    bit_reader rd;
-    rd.words = data, rd.acc = 0, rd.w = 0, rd.cnt = 0, rd.widx = -1, rd.pad = 0, rd.ff = false;
-    rd.pos = min(max(unit_off[u], 0), g.data_bytes);
-    rd.end = min(max(unit_off[u + 1], rd.pos), g.data_bytes);
-    short *cf = coef + (size_t)f * g.coef_frame;
-    int pred[3] = {0, 0, 0};
-    int mxi = (int)(m0 % g.mx), myi = (int)(m0 / g.mx);
-    bool ok = true;
-    for (long long m = m0; m < m1 && ok; ++m) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            if (c >= g.ncomp || !ok) continue;
-            for (int vy = 0; vy < g.v[c] && ok; ++vy)
-                for (int vx = 0; vx < g.h[c] && ok; ++vx) {
-                    const long long blk = g.cblk[c] + (long long)(myi * g.v[c] + vy) * g.bw[c] + mxi * g.h[c] + vx;
-                    ok = decode_block(rd, cf + blk * 64, pred[c], T[2 * c], T[2 * c + 1], zig);
-                }
-        }
-        if (++mxi == g.mx) mxi = 0, ++myi;
-    }
-    const int st = rd.ran_short() ? A3D_JPEG_SHORT : ok ? 0 : A3D_JPEG_BAD_CODE;
-    if (st) atomicMax(reinterpret_cast<int *>(cf + g.cblk[3] * 64), st);
-}
-
-// ---- entropy, self-synchronising (a3d_jpeg_decode_split) --------------------------------------------------------------------------------
+// ---- entropy: the walk -------------------------------------------------------------------------------------------------------------------
 // A unit's stuffed bytes are cut into subsequences of S = max(split_bytes, ceil(unit bytes / lpu)) bytes, one lane each; the lpu lanes
 // of a unit (a power of two, 1024 at the most) sit in one workgroup, and a workgroup holds blockDim / lpu units of one frame, so all
 // synchronisation is LDS and barriers.  A decoder state between two syntax elements is (position, slot within the MCU, zig-zag index;
@@ -251,10 +130,11 @@ __global__ __launch_bounds__(EN_LANES) void jpeg_decode_entropy_kernel(const uns
 // sum of the differences in scan order, modulo 2^16, turns them into DC values behind a barrier.
 //
 // What keeps every access inside the call's buffers: the reader fetches bytes of [lo, hi) of its unit only, both clamped to the data
-// (zeros beyond); a block's ordinal is tested against the unit's block count before its address is formed, so it lies in the unit's
-// own MCUs; a coefficient index is at most 63 by the tests of `element`; LDS is indexed by the thread and by its unit within the
-// workgroup.  Every loop is bounded: a walk by its end bit or by the unit's blocks (an element moves the index forward and a block
-// takes at most 64 of them), the rounds by lpu.
+// (zeros beyond); a code's symbol index is below the table's symbol count by construction of the first-code rows; a block's ordinal
+// is tested against the unit's block count before its address is formed, so it lies in the unit's own MCUs; a coefficient index is
+// at most 63 by the tests of `element`; LDS is indexed by the thread and by its unit within the workgroup.  Every loop is bounded: a
+// walk by its end bit or by the unit's blocks (an element moves the index forward and a block takes at most 64 of them), the rounds
+// by lpu.
 constexpr int SP_LANES = 1024;     // threads of a workgroup, and lanes of a unit, at the most
 constexpr int SP_SATURATE = 1 << 30;  // above every unit's block count (201 M for 65535 x 65535 at 4:4:4)
 
@@ -303,7 +183,7 @@ struct pos_reader {
         bp += n + 8 * __popc(m);
         cnt -= n;
     }
-    // As bit_reader::symbol: the next symbol of table t, or -1 where the next 16 bits start no code (they are consumed).
+    // The next symbol of table t, or -1 where the next 16 bits start no code (they are consumed).  Leaves at least 16 bits in `acc`.
     __device__ __forceinline__ int symbol(const huff_lds &t) {
         if (cnt < 32) refill();
         const unsigned int p = (unsigned int)(acc >> (cnt - 16)) & 0xFFFFu;
@@ -361,6 +241,16 @@ __device__ __forceinline__ unsigned long long pack_state(const long long bp, con
     return (unsigned long long)bp << 9 | (unsigned int)(slot << 6 | idx);
 }
 
+// The other way, and what follows every element: a block that is done gives way to the next slot of the MCU (hv luma blocks, then
+// one per chroma component; nslot in all).  (The component of a slot, slot < hv ? 0 : slot - hv + 1, stays at its three sites: as a
+// function it changed the kernel's instruction selection; MEASUREMENTS.md, "JPEG decode: one entropy kernel".)
+__device__ __forceinline__ void unpack_state(const unsigned long long state, int &slot, int &idx) {
+    slot = (int)(state >> 6) & 7, idx = (int)state & 63;
+}
+__device__ __forceinline__ void next_slot_if_done(int &slot, int &idx, const int nslot) {
+    if (idx == 64) idx = 0, slot = slot + 1 == nslot ? 0 : slot + 1;
+}
+
 // Inclusive sum over the lpu lanes of a unit (lpu a power of two, segments aligned to it), through s[blockDim]; SAT: saturating at
 // SP_SATURATE (the operands are not negative), else modulo 2^32.  Every thread of the workgroup calls it; it ends behind a barrier.
 template <bool SAT>
@@ -386,15 +276,14 @@ __global__ __launch_bounds__(SP_LANES) void jpeg_decode_split_kernel(const unsig
     __shared__ unsigned int s_scan[SP_LANES];
     __shared__ int s_bad[SP_LANES], s_lim[SP_LANES];  // per unit of the workgroup: its first flagged lane; the blocks its DC sums cover
     const int t = threadIdx.x, f = blockIdx.y;
-    const int *unit_off = meta, *frame_unit = meta + g.n_units + 1, *frame_ri = frame_unit + g.F + 1, *frame_set = frame_ri + g.F;
-    const int set = min(max(frame_set[f], 0), g.n_sets - 1);
-    build_tables(T, zig, sets + (size_t)set * A3D_JPEG_TABSET_BYTES + SET_QUANT, 2 * g.ncomp, t, (int)blockDim.x);
+    const dec_meta mt(meta, g);
+    build_tables(T, zig, mt.table_set(sets, g, f) + SET_QUANT, 2 * g.ncomp, t, (int)blockDim.x);
 
     const int ul = t / lpu, jl = t - ul * lpu;  // the unit within the workgroup, the lane within the unit
-    const int u0 = frame_unit[f], u1 = frame_unit[f + 1];
+    const int u0 = mt.frame_unit[f], u1 = mt.frame_unit[f + 1];
     const long long k = (long long)blockIdx.x * ((int)blockDim.x / lpu) + ul;  // the unit within the frame
     const long long total = (long long)g.mx * g.my;
-    const long long ri = frame_ri[f] > 0 ? frame_ri[f] : total;
+    const long long ri = mt.frame_ri[f] > 0 ? mt.frame_ri[f] : total;
     const long long m0 = k * ri;
     const bool unit_ok = u0 >= 0 && u1 <= g.n_units && k < (long long)u1 - u0 && m0 < total;
     const int hv = g.hs * g.vs, nslot = g.ncomp == 1 ? 1 : hv + 2;
@@ -402,8 +291,8 @@ __global__ __launch_bounds__(SP_LANES) void jpeg_decode_split_kernel(const unsig
     int lo = 0, len = 0;
     if (unit_ok) {
         const int u = u0 + (int)k;
-        lo = min(max(unit_off[u], 0), g.data_bytes);
-        len = min(max(unit_off[u + 1], lo), g.data_bytes) - lo;
+        lo = min(max(mt.unit_off[u], 0), g.data_bytes);
+        len = min(max(mt.unit_off[u + 1], lo), g.data_bytes) - lo;
     }
     const int S = max(max(split, (len + lpu - 1) / lpu), 1);
     const int n_sub = max((len + S - 1) / S, 1);
@@ -427,7 +316,8 @@ __global__ __launch_bounds__(SP_LANES) void jpeg_decode_split_kernel(const unsig
         if (need) {
             pos_reader rd;
             rd.start(data, lo, lo + len, (long long)(entry >> 9));
-            int slot = (int)(entry >> 6) & 7, idx = (int)entry & 63;
+            int slot, idx;
+            unpack_state(entry, slot, idx);
             begun = 0, bad_at = -1;
             while (rd.bp < end_bit) {
                 const int c = slot < hv ? 0 : slot - hv + 1;
@@ -437,7 +327,7 @@ __global__ __launch_bounds__(SP_LANES) void jpeg_decode_split_kernel(const unsig
                     if (bad_at < 0) bad_at = begun;
                     idx = 64;
                 }
-                if (idx == 64) idx = 0, slot = slot + 1 == nslot ? 0 : slot + 1;
+                next_slot_if_done(slot, idx, nslot);
             }
             exit_state = pack_state(rd.bp, slot, idx);
         }
@@ -458,14 +348,15 @@ __global__ __launch_bounds__(SP_LANES) void jpeg_decode_split_kernel(const unsig
     if (active && prefix <= n_blocks && jl <= s_bad[ul]) {
         pos_reader rd;
         rd.start(data, lo, lo + len, (long long)(entry >> 9));
-        int slot = (int)(entry >> 6) & 7, idx = (int)entry & 63;
+        int slot, idx;
+        unpack_state(entry, slot, idx);
         int n = 0, st = 0;  // blocks begun here
         short *dst = nullptr;
         auto block_at = [&](const int ordinal, const int sl) -> short * {
             const long long m = m0 + ordinal / nslot;
             const int mxi = (int)(m % g.mx), myi = (int)(m / g.mx);
             const int c = sl < hv ? 0 : sl - hv + 1, vy = c == 0 ? sl / g.hs : 0, vx = c == 0 ? sl - vy * g.hs : 0;
-            return cf + (g.cblk[c] + (long long)(myi * g.v[c] + vy) * g.bw[c] + mxi * g.h[c] + vx) * 64;
+            return cf + g.block(c, mxi, myi, vy, vx) * 64;
         };
         if (idx > 0 && prefix > 0) dst = block_at(prefix - 1, slot);
         for (;;) {
@@ -484,7 +375,7 @@ __global__ __launch_bounds__(SP_LANES) void jpeg_decode_split_kernel(const unsig
                 break;
             }
             if (kk >= 0 && val != 0 && dst) dst[zig[kk]] = (short)val;
-            if (idx == 64) idx = 0, slot = slot + 1 == nslot ? 0 : slot + 1;
+            next_slot_if_done(slot, idx, nslot);
         }
         if (st) atomicMax(reinterpret_cast<int *>(cf + g.cblk[3] * 64), st);
     }
@@ -500,7 +391,7 @@ __global__ __launch_bounds__(SP_LANES) void jpeg_decode_split_kernel(const unsig
             const long long m = m0 + q / hvc;
             const int wi = (int)(q % hvc), vy = wi / g.h[c], vx = wi - vy * g.h[c];
             const int mxi = (int)(m % g.mx), myi = (int)(m / g.mx);
-            return cf + (g.cblk[c] + (long long)(myi * g.v[c] + vy) * g.bw[c] + mxi * g.h[c] + vx) * 64;
+            return cf + g.block(c, mxi, myi, vy, vx) * 64;
         };
         unsigned int sum = 0;
         for (long long q = q0; q < q1; ++q) sum += (unsigned int)(int)*dc_at(q);
@@ -549,8 +440,7 @@ __global__ __launch_bounds__(256) void jpeg_decode_idct_kernel(short *__restrict
     int *my = sA + b * 8 * ID_LD;
     bool out = false;
     if (live) {
-        const int set = min(max(meta[g.n_units + 1 + g.F + 1 + g.F + f], 0), g.n_sets - 1);
-        const uint2 qv = *reinterpret_cast<const uint2 *>(sets + (size_t)set * A3D_JPEG_TABSET_BYTES + c * 64 + r * 8);
+        const uint2 qv = *reinterpret_cast<const uint2 *>(dec_meta(meta, g).table_set(sets, g, f) + c * 64 + r * 8);
         const uint4 cv = *reinterpret_cast<const uint4 *>(coef + (size_t)f * g.coef_frame + blk * 64 + r * 8);
         const unsigned int cw[4] = {cv.x, cv.y, cv.z, cv.w}, qw[2] = {qv.x, qv.y};
 #pragma unroll
@@ -660,10 +550,9 @@ extern "C" int a3d_jpeg_decode_scratch(int H, int W, int ncomp, int hs, int vs, 
     return A3D_OK;
 }
 
-// Both entry points: split_bytes = 0 is a3d_jpeg_decode's one lane per unit, above it a3d_jpeg_decode_split's entropy launch.
-static int decode_launch(const a3d_jpeg_decode_desc *d, const int split_bytes, void *stream) {
+extern "C" int a3d_jpeg_decode_split(const a3d_jpeg_decode_desc *d, int split_bytes, void *stream) {
     dec_geom g;
-    if (!d || !make_geom(d->F, d->H, d->W, d->pitch, d->ncomp, d->hs, d->vs, &g)) return A3D_ERR_ARG;
+    if (!d || split_bytes < 1 || !make_geom(d->F, d->H, d->W, d->pitch, d->ncomp, d->hs, d->vs, &g)) return A3D_ERR_ARG;
     if (d->F == 0) return A3D_OK;
     if (d->F > 65535 || d->n_units < 1 || d->n_sets < 1 || d->data_bytes < 0 || d->data_bytes > 0x7FFFFFFFll) return A3D_ERR_ARG;
     if (!d->unit_off || !d->frame_unit || !d->frame_ri || !d->frame_set || !d->sets || !d->d_meta || !d->d_sets || !d->coef || !d->planes || !d->rgb ||
@@ -698,25 +587,19 @@ static int decode_launch(const a3d_jpeg_decode_desc *d, const int split_bytes, v
     const long long n_blocks = (long long)d->F * g.cblk[3], id_grid = (n_blocks + ID_BLOCKS - 1) / ID_BLOCKS;
     const int groups = (d->W + 15) / 16;
     const long long n_groups = (long long)d->F * d->H * groups, co_grid = (n_groups + 255) / 256;
-    // split: the lanes of a unit are the power of two that gives the longest unit of the call subsequences of split_bytes, and a
-    // workgroup is as many units of `lpu` lanes as the frame with the most units fills, 1024 threads at the most.
-    int lpu = 1, threads = EN_LANES;
-    if (split_bytes > 0) {
-        while (lpu < SP_LANES && (long long)lpu * split_bytes < longest) lpu *= 2;
-        const long long step = lpu > 64 ? lpu : 64, want = (most * lpu + step - 1) / step * step;
-        threads = (int)(want < SP_LANES ? want : SP_LANES);
-    }
+    // The lanes of a unit are the power of two that gives the longest unit of the call subsequences of split_bytes, and a workgroup
+    // is as many units of `lpu` lanes as the frame with the most units fills, 1024 threads at the most.
+    int lpu = 1;
+    while (lpu < SP_LANES && (long long)lpu * split_bytes < longest) lpu *= 2;
+    const long long step = lpu > 64 ? lpu : 64, want = (most * lpu + step - 1) / step * step;
+    const int threads = (int)(want < SP_LANES ? want : SP_LANES);
     const long long per_group = threads / lpu, en_grid = (most + per_group - 1) / per_group;
     if (id_grid > 0x7FFFFFFFll || co_grid > 0x7FFFFFFFll || en_grid > 0x7FFFFFFFll) return A3D_ERR_ARG;
     const int vec = (uintptr_t)d->rgb % 16 == 0 && ((size_t)d->pitch * 3) % 16 == 0;
     a3d_begin();
     if (hipMemsetAsync(d->coef, 0, (size_t)d->F * g.coef_frame * sizeof(short), (hipStream_t)stream) != hipSuccess) return A3D_ERR_LAUNCH;
-    if (split_bytes > 0)
-        hipLaunchKernelGGL(jpeg_decode_split_kernel, dim3((unsigned int)en_grid, (unsigned int)d->F), dim3(threads), 0, (hipStream_t)stream,
-                           reinterpret_cast<const unsigned int *>(d->d_data), d->d_meta, d->d_sets, d->coef, g, split_bytes, lpu);
-    else
-        hipLaunchKernelGGL(jpeg_decode_entropy_kernel, dim3((unsigned int)en_grid, (unsigned int)d->F), dim3(EN_LANES), 0, (hipStream_t)stream,
-                           reinterpret_cast<const unsigned int *>(d->d_data), d->d_meta, d->d_sets, d->coef, g);
+    hipLaunchKernelGGL(jpeg_decode_split_kernel, dim3((unsigned int)en_grid, (unsigned int)d->F), dim3(threads), 0, (hipStream_t)stream,
+                       reinterpret_cast<const unsigned int *>(d->d_data), d->d_meta, d->d_sets, d->coef, g, split_bytes, lpu);
     hipLaunchKernelGGL(jpeg_decode_idct_kernel, dim3((unsigned int)id_grid), dim3(256), 0, (hipStream_t)stream, d->coef, d->d_meta, d->d_sets, d->planes,
                        g, n_blocks);
     hipLaunchKernelGGL(jpeg_decode_colour_kernel, dim3((unsigned int)co_grid), dim3(256), 0, (hipStream_t)stream, d->planes, d->coef, d->rgb, d->status, g,
@@ -724,8 +607,4 @@ static int decode_launch(const a3d_jpeg_decode_desc *d, const int split_bytes, v
     return a3d_check_launch();
 }
 
-extern "C" int a3d_jpeg_decode(const a3d_jpeg_decode_desc *d, void *stream) { return decode_launch(d, 0, stream); }
-
-extern "C" int a3d_jpeg_decode_split(const a3d_jpeg_decode_desc *d, int split_bytes, void *stream) {
-    return split_bytes < 1 ? A3D_ERR_ARG : decode_launch(d, split_bytes, stream);
-}
+extern "C" int a3d_jpeg_decode(const a3d_jpeg_decode_desc *d, void *stream) { return a3d_jpeg_decode_split(d, A3D_JPEG_SPLIT_BYTES, stream); }

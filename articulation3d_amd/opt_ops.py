@@ -318,8 +318,8 @@ def jpeg_decode_scratch(H: int, W: int, ncomp: int, hs: int, vs: int):
 
 def jpeg_decode_into(rgb: torch.Tensor, status: torch.Tensor, data: torch.Tensor, data_bytes: int, meta, meta_dev: torch.Tensor, sets,
                      sets_dev: torch.Tensor, n_units: int, ncomp: int, hs: int, vs: int, coef: torch.Tensor, planes: torch.Tensor,
-                     split_bytes: int = 0) -> None:
-    """a3d_jpeg_decode (split_bytes = 0) or a3d_jpeg_decode_split (any other value: the library refuses what is below 1) into
+                     split_bytes: int = None) -> None:
+    """a3d_jpeg_decode (split_bytes None) or a3d_jpeg_decode_split (an integer: the library refuses what is below 1) into
     caller-owned buffers (no synchronisation).  rgb uint8 [F,H,W,3] on the device (dense or a column range of
     wider rows), status int32 [F]; data uint8 on the device, a multiple of 4 bytes holding `data_bytes` of units; meta a contiguous
     int32 numpy array [unit_off (n_units+1) | frame_unit (F+1) | frame_ri (F) | frame_set (F)] and sets a uint8 numpy array
@@ -341,7 +341,7 @@ def jpeg_decode_into(rgb: torch.Tensor, status: torch.Tensor, data: torch.Tensor
     d.frame_ri, d.frame_set = C.cast(at + 4 * (n_units + 1 + F_ + 1), ip), C.cast(at + 4 * (n_units + 1 + 2 * F_ + 1), ip)
     d.sets = C.cast(sets.ctypes.data, C.POINTER(C.c_ubyte))
     d.d_data, d.d_meta, d.d_sets, d.coef, d.planes, d.rgb, d.status = _p(data), _p(meta_dev), _p(sets_dev), _p(coef), _p(planes), _p(rgb), _p(status)
-    if split_bytes == 0:
+    if split_bytes is None:
         _lib.check(_lib.lib().a3d_jpeg_decode(C.byref(d), _stream()), "a3d_jpeg_decode")
     else:
         _lib.check(_lib.lib().a3d_jpeg_decode_split(C.byref(d), int(split_bytes), _stream()), "a3d_jpeg_decode_split")

@@ -15,8 +15,8 @@ tests/jpeg_decode_ref.py): baseline JPEG, grey or 4:4:4 / 4:2:2 / 4:2:0, any tab
 bytes libjpeg's default decoder gives.
 
     jpeg_parse(data)                                     -> JPEGInfo (pure Python); ValueError for what the decoder's law leaves out
-    jpeg_decode(jpegs, device, chunk, strict, entropy)   -> uint8 [F,H,W,3] RGB on the device; entropy="split" decodes a scan
-                                                            without restart intervals by many lanes at once (a3d_jpeg_decode_split)
+    jpeg_decode(jpegs, device, chunk, strict)            -> uint8 [F,H,W,3] RGB on the device; a restart interval, or a whole scan
+                                                            without them, is decoded by many lanes at once
     MJPEGReader(path)                                    -> .width, .height, .fps, len(), reader[i], reader[a:b]; a context manager
 
 The container is a plain RIFF `AVI ` file (hdrl: avih + one strl of type vids / MJPG with a BITMAPINFOHEADER; a movi list of 00dc
@@ -254,7 +254,7 @@ class MJPEGWriter:
 # ---------------------------------------------------------------------------------------------------------------------
 _NOT_DATA = re.compile(b"\xff[^\x00\xd0-\xd7]")  # in entropy-coded data FF is followed by 00 or, as a restart marker, by D0 .. D7
 _RST = re.compile(b"\xff[\xd0-\xd7]")
-JPEG_SPLIT_BYTES = 32  # bytes of a subsequence of jpeg_decode(entropy="split") by default: the fastest of 32 .. 256 (MEASUREMENTS.md, "JPEG decode")
+JPEG_SPLIT_BYTES = _lib.JPEG_SPLIT_BYTES  # bytes of a subsequence of jpeg_decode by default: a3d_jpeg_decode's own (include/a3d.h)
 JPEG_STATUS = {_lib.JPEG_RANGE: "RANGE", _lib.JPEG_BAD_CODE: "BAD_CODE", _lib.JPEG_SHORT: "SHORT"}
 
 
@@ -413,18 +413,16 @@ def jpeg_parse(data: bytes) -> JPEGInfo:
     return JPEGInfo(height, width, ncomp, sampling[0][0], sampling[0][1], tuple(q_out), tuple(h_out), restart, (lo, hi), tuple(units))
 
 
-def jpeg_decode(jpegs: Sequence[bytes], device="cuda", chunk: int = 8, strict: bool = True, entropy: str = "unit", split_bytes: int = None):
+def jpeg_decode(jpegs: Sequence[bytes], device="cuda", chunk: int = 8, strict: bool = True, split_bytes: int = None):
     """F baseline JPEG files of one size and one sampling -> uint8 [F,H,W,3] RGB on the device, byte for byte what libjpeg's
     default decoder returns (include/a3d.h states the law).  The host parses the headers and uploads the entropy-coded bytes and one table set per
     distinct set of tables of the call; `chunk` frames are decoded per a3d_jpeg_decode call, and the host prepares a chunk while the
     device decodes the one before.  A frame's pixels do not depend on the frames beside it or on `chunk`.  With `strict` a frame
     whose status is not 0 raises ValueError with its index and the code (SHORT, BAD_CODE, RANGE); without, -> (frames, status
-    int32 [F] on the host).  `entropy`: "unit" gives every restart interval (the whole scan without them) one lane; "split" cuts a
-    unit into subsequences of `split_bytes` (None: JPEG_SPLIT_BYTES) that synchronise themselves, the same bytes and status."""
-    if entropy not in ("unit", "split"):
-        raise ValueError(f"entropy {entropy!r}: 'unit' or 'split'")
-    split = 0 if entropy == "unit" else JPEG_SPLIT_BYTES if split_bytes is None else int(split_bytes)
-    if entropy == "split" and split < 1:
+    int32 [F] on the host).  A unit (a restart interval, the whole scan without them) is cut into subsequences of `split_bytes`
+    (None: JPEG_SPLIT_BYTES, the library's default) that synchronise themselves; bytes and status do not depend on the size."""
+    split = None if split_bytes is None else int(split_bytes)
+    if split is not None and split < 1:
         raise ValueError(f"split_bytes {split_bytes!r}: at least 1")
     infos = []
     for i, j in enumerate(jpegs):

@@ -1245,15 +1245,12 @@ typedef struct {
  * the device copies and clamp whatever they find there.  A3D_ERR_ARG before any launch: a null pointer, a misaligned buffer, a
  * geometry outside the law, pitch < W, F outside 0 .. 65535, an offset table that is not monotonic or does not start at 0 and end
  * at data_bytes / n_units, a frame whose unit count is not ceil(mx my / interval), a table index out of range, a Huffman
- * specification whose codes do not fit their lengths, or data_bytes above 2^31 - 1.  F == 0 is a no-op. */
-int a3d_jpeg_decode(const a3d_jpeg_decode_desc *d, void *stream);
-/* a3d_jpeg_decode with a self-synchronising entropy launch: a unit (above all a scan without restart intervals) is decoded by many
- * lanes at once.  The same descriptor, scratch, validation, A3D_ERR_ARG cases and status codes; split_bytes < 1 is A3D_ERR_ARG as well.
- * The law: for every input status[f] is what a3d_jpeg_decode gives, and every frame whose status is 0 has the same RGB bytes (of a
- * frame with another status nothing is asked, as above).  No stream content can make a read or a write leave the buffers of the call,
- * and a unit writes only its own blocks.  The result does not depend on split_bytes, on F or on the frames beside a frame: it is
- * exact by construction, never by a stream happening to synchronise.
- *   scheme    a unit's stuffed bytes are cut into subsequences of S = max(split_bytes, ceil(unit bytes / L)) bytes, one lane each; the
+ * specification whose codes do not fit their lengths, or data_bytes above 2^31 - 1.  F == 0 is a no-op.
+ * The entropy launch synchronises itself: a unit (above all a scan without restart intervals) is decoded by many lanes at once, in
+ * subsequences of A3D_JPEG_SPLIT_BYTES.  No stream content can make a read or a write leave the buffers of the call, and a unit
+ * writes only its own blocks.  The result does not depend on the subsequence size, on F or on the frames beside a frame: it is exact
+ * by construction, never by a stream happening to synchronise.
+ *   scheme    a unit's stuffed bytes are cut into subsequences of S = max(subsequence size, ceil(unit bytes / L)) bytes, one lane each; the
  *             L <= 1024 lanes of a unit share a workgroup (short units share one), so nothing synchronises across workgroups.  A
  *             decoder state between two syntax elements is (bit position, block slot within the MCU, zig-zag index; 0 = a DC symbol
  *             is next).  Round 0 walks every subsequence from (its first bit, slot 0, index 0), the first from the unit's start; in
@@ -1265,7 +1262,15 @@ int a3d_jpeg_decode(const a3d_jpeg_decode_desc *d, void *stream);
  *             inside the unit's blocks ends the unit as in the law, and the last lane reads zeros past the unit until its blocks are
  *             done (SHORT over BAD_CODE, the cause).  A second walk from the true entries stores AC values and DC differences, and a
  *             sum per unit and component, modulo 2^16, turns the differences into DC values.
- * The memset, the dequantise + IDCT launch and the upsample + colour launch are a3d_jpeg_decode's own. */
+ *   cost      the launch is the latency of one lane's walks.  Against one lane per unit walking once (the launch this one replaced) it is
+ *             2.1 - 17 x shorter where units are longer than some 1 KB, and 1.1 - 2.1 x LONGER where a unit is one or a few
+ *             subsequences (restart intervals of 1 - 5 MCUs of a 480 x 640 frame: 300 - 710 us against 150 - 500 us for 8 - 32
+ *             frames), which end to end costs up to 18 % of the frames/s of such a stream at 8 frames per call and nothing
+ *             measurable at 32 (MEASUREMENTS.md, "JPEG decode: one entropy kernel").  */
+#define A3D_JPEG_SPLIT_BYTES 32 /* the fastest of 32 .. 256 for three of four classes of stream (MEASUREMENTS.md, "JPEG decode") */
+int a3d_jpeg_decode(const a3d_jpeg_decode_desc *d, void *stream);
+/* a3d_jpeg_decode with an explicit subsequence size in place of A3D_JPEG_SPLIT_BYTES: the same descriptor, scratch, validation,
+ * A3D_ERR_ARG cases, status codes and result; split_bytes < 1 is A3D_ERR_ARG as well. */
 int a3d_jpeg_decode_split(const a3d_jpeg_decode_desc *d, int split_bytes, void *stream);
 
 #ifdef __cplusplus

@@ -414,6 +414,71 @@ def patched_sampling(data: bytes, hv: int) -> bytes:
     return bytes(out)
 
 
+def with_scan(data: bytes, blocks) -> bytes:
+    """The one-component file `data` with its scan replaced by one assembled from syntax elements: per block a list of ('dc', v) (the
+    DC difference v), ('ac', run, v), 'ZRL', 'EOB', or ('dc_symbol', s) (the DC code of symbol s, no value bits behind it).  Codes
+    are the file's own tables'; the last byte is padded with 1-bits and every FF is stuffed."""
+    (_h, _v, _q, dc, ac), = parse(data).comps
+    dc, ac = ({sym: key for key, sym in _codes(*t).items()} for t in (dc, ac))  # symbol -> (length, code)
+    bits = ""
+
+    def put(table, symbol, v=0):
+        nonlocal bits
+        length, code = table[symbol]
+        size = abs(v).bit_length()
+        bits += format(code, f"0{length}b") + (format(v if v > 0 else v + (1 << size) - 1, f"0{size}b") if size else "")
+
+    for block in blocks:
+        for e in block:
+            if e == "ZRL":
+                put(ac, 0xF0)
+            elif e == "EOB":
+                put(ac, 0x00)
+            elif e[0] == "dc":
+                put(dc, abs(e[1]).bit_length(), e[1])
+            elif e[0] == "ac":
+                put(ac, e[1] << 4 | abs(e[2]).bit_length(), e[2])
+            else:
+                put(dc, e[1])
+    bits += "1" * (-len(bits) % 8)
+    scan = int(bits, 2).to_bytes(len(bits) // 8, "big").replace(b"\xff", b"\xff\x00")
+    return data[:segments(data)[-1][2]] + scan + b"\xff\xd9"
+
+
+def patched_dc_symbol(data: bytes, old: int, new: int) -> bytes:
+    """The symbol `old` of every DC Huffman table replaced by `new`: the same codes, another alphabet."""
+    out = bytearray(data)
+    for m, lo, hi in segments(data):
+        at = lo + 4
+        while m == 0xC4 and at < hi:
+            n = sum(data[at + 1:at + 17])
+            if data[at] >> 4 == 0:
+                out[at + 17 + data[at + 17:at + 17 + n].index(old)] = new
+            at += 17 + n
+    return bytes(out)
+
+
+# A block's grammar at its edges (the law's status beside each), every one in front of an ordinary block that comes out wrong unless
+# the state behind the edge is right: the last coefficient without an EOB, a ZRL that lands on 64 exactly, a ZRL past 64, a run past 63.
+EDGE_TAIL = [("dc", 3), ("ac", 0, 4), ("ac", 2, -9), "EOB"]
+EDGE_BLOCKS = {
+    "coefficient_63_no_eob": ([("dc", 5), "ZRL", "ZRL", "ZRL", ("ac", 14, -3)], OK),
+    "zrl_lands_on_64": ([("dc", 5), ("ac", 14, 2), ("ac", 15, 1), ("ac", 15, -1), "ZRL"], OK),
+    "zrl_to_65": ([("dc", 5), "ZRL", "ZRL", "ZRL", "ZRL"], BAD_CODE),
+    "run_past_63": ([("dc", 5), "ZRL", "ZRL", "ZRL", ("ac", 15, 1)], BAD_CODE),
+    "dc_symbol_16": ([("dc_symbol", 16), "EOB"], BAD_CODE),
+}
+
+
+def edge_stream(name: str) -> bytes:
+    """EDGE_BLOCKS[name] and EDGE_TAIL as the two blocks of an 8 x 16 grey file (dc_symbol_16: category 11 of its DC table, which no
+    8-bit image needs, is renamed 16: category > 15)."""
+    base = pil_jpeg(grey_image(8, 16), 90)
+    if name == "dc_symbol_16":
+        base = patched_dc_symbol(base, 11, 16)
+    return with_scan(base, [EDGE_BLOCKS[name][0], EDGE_TAIL])
+
+
 def cut_before_sos(data: bytes) -> bytes:
     return data[:[lo for m, lo, _hi in segments(data) if m == 0xDA][0]]
 

@@ -1,7 +1,7 @@
 """GPU suite: a3d_jpeg_decode_split (csrc/jpeg_decode.hip), the entropy launch that cuts a unit into subsequences which synchronise
-themselves, through video.jpeg_decode(..., entropy="split", split_bytes=S, strict=False): byte for byte tests/jpeg_decode_ref.py with
-status 0, for every subsequence size, and the law's status for damaged streams.  tests/jpeg_split_ref.py (held to the law by
-tests/test_jpeg_split_host.py) says which fixture stresses what.  Sizes are H x W."""
+themselves, at explicit subsequence sizes through video.jpeg_decode(..., split_bytes=S, strict=False): byte for byte
+tests/jpeg_decode_ref.py with status 0, for every subsequence size, and the law's status for damaged streams.  tests/jpeg_split_ref.py
+(held to the law by tests/test_jpeg_split_host.py) says which fixture stresses what.  Sizes are H x W."""
 import numpy as np
 import pytest
 import torch
@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 def gpu(jpegs, split, **kw):
     from articulation3d_amd import video
 
-    frames, status = video.jpeg_decode(jpegs, strict=False, entropy="split", split_bytes=split, **kw)
+    frames, status = video.jpeg_decode(jpegs, strict=False, split_bytes=split, **kw)
     return frames.cpu().numpy(), status.tolist()
 
 
@@ -120,24 +120,36 @@ def test_status_codes_and_their_neighbours():
             assert np.array_equal(frames[k], ref(loose[k])[0])
 
 
-def test_real_sizes_equal_the_one_lane_path():
+def test_real_sizes_equal_pil():
     """480 x 640 at 4:2:0 and 480 x 2560 at 4:4:4, quality 90, no restart intervals, at the default subsequence size (the second
-    scan is long enough for the size to be raised above it).  The law in numpy takes minutes here; the one-lane path is pinned to it."""
-    from articulation3d_amd import video
+    scan is long enough for the size to be raised above it).  The law in numpy takes minutes here; tests/test_jpeg_decode_host.py
+    holds it to PIL byte for byte, so PIL stands for it."""
+    from articulation3d_amd import _lib, video
 
+    assert video.JPEG_SPLIT_BYTES == _lib.JPEG_SPLIT_BYTES == 32
     for H, W, sub in ((480, 640, 2), (480, 2560, 0)):
         data = D.pil_jpeg(M.smooth_frames(1, H, W)[0], 90, sub)
         info = video.jpeg_parse(data)
         assert info.restart == 0 and (sub == 2 or info.scan[1] - info.scan[0] > 1024 * video.JPEG_SPLIT_BYTES)
-        want, want_status = video.jpeg_decode([data], strict=False)
-        got, status = video.jpeg_decode([data], strict=False, entropy="split")
-        assert want_status.tolist() == [0] and status.tolist() == [0] and torch.equal(got, want)
-    with pytest.raises(ValueError, match="entropy"):
-        video.jpeg_decode([data], entropy="lanes")
+        got, status = video.jpeg_decode([data], strict=False)
+        assert status.tolist() == [0] and np.array_equal(got[0].cpu().numpy(), D.pil_decode(data))
 
 
-def test_bad_split_sizes_are_refused_before_any_launch(monkeypatch):
-    from articulation3d_amd import _lib, opt_ops, video
+@pytest.mark.parametrize("name", list(D.EDGE_BLOCKS))
+def test_grammar_edges(name):
+    """Scans assembled from syntax elements (tests/test_jpeg_split_host.py holds the law's status and the model on them): the kernel
+    equals the law, status and, where that is 0, bytes, at sizes that cut these 8 .. 17 byte units, above them, and at the default."""
+    data = D.edge_stream(name)
+    want, want_status = ref(data)
+    assert want_status == D.EDGE_BLOCKS[name][1]
+    for split in (1, 2, 4, 64, None):
+        frames, status = gpu([data], split)
+        assert status == [want_status], split
+        assert want_status != D.OK or np.array_equal(frames[0], want), split
+
+
+def test_bad_split_sizes_are_refused_before_any_launch():
+    from articulation3d_amd import opt_ops, video
 
     data = D.pil_jpeg(M.noise(16, 16, 1), 90, 2)
     info = video.jpeg_parse(data)
@@ -159,14 +171,10 @@ def test_bad_split_sizes_are_refused_before_any_launch(monkeypatch):
         call(-1)
     with pytest.raises(RuntimeError, match="a3d_jpeg_decode_split failed with A3D_ERR_ARG"):
         call(4, nbytes=n - 1)  # the descriptor's own cases hold here too: offsets that do not end at data_bytes
-    lib = _lib.lib()
-    real = lib.a3d_jpeg_decode_split
-    with monkeypatch.context() as m:  # a zero reaches the library only through the raw binding (jpeg_decode_into reads it as "unit")
-        m.setattr(lib, "a3d_jpeg_decode_split", lambda d, _split, stream: real(d, 0, stream))
-        with pytest.raises(RuntimeError, match="a3d_jpeg_decode_split failed with A3D_ERR_ARG"):
-            call(4)
+    with pytest.raises(RuntimeError, match="a3d_jpeg_decode_split failed with A3D_ERR_ARG"):
+        call(0)
     with pytest.raises(ValueError, match="split_bytes"):
-        video.jpeg_decode([data], entropy="split", split_bytes=0)
+        video.jpeg_decode([data], split_bytes=0)
     torch.cuda.synchronize()
     assert (rgb == 0x5A).all() and status.tolist() == [-7]
     call(4)
@@ -175,14 +183,15 @@ def test_bad_split_sizes_are_refused_before_any_launch(monkeypatch):
 
 def test_the_tool_decodes_a_folder_of_plain_files_on_the_gpu(monkeypatch):
     """PIL's default output (no restart intervals) through tools/inference.py's decode_images under --decoder gpu: PIL's bytes, by
-    the split path."""
+    one GPU call."""
     frames = M.smooth_frames(3, 96, 128)
     blobs = [D.pil_jpeg(fr, 90) for fr in frames]
     from articulation3d_amd import video
 
     assert all(video.jpeg_parse(b).restart == 0 for b in blobs)
-    real, asked = video.jpeg_decode, []
-    monkeypatch.setattr(video, "jpeg_decode", lambda *a, **kw: (asked.append(kw.get("entropy")), real(*a, **kw))[1])
+    real, calls = video.jpeg_decode, []
+    monkeypatch.setattr(video, "jpeg_decode", lambda *a, **kw: calls.append(real(*a, **kw)) or calls[-1])
     got = _inference().decode_images(blobs, "gpu")
-    assert asked == ["split"]
+    (frames, status), = calls
+    assert status.tolist() == [0, 0, 0] and np.array_equal(frames.cpu().numpy(), got)
     assert got.dtype == np.uint8 and np.array_equal(got, np.stack([D.pil_decode(b) for b in blobs]))

@@ -99,6 +99,23 @@ def test_damaged_streams():
         hold(garbage_scan(seed), (4, 64))
 
 
+@pytest.mark.parametrize("name", list(D.EDGE_BLOCKS))
+def test_grammar_edges(name):
+    """Scans assembled from syntax elements (D.with_scan): the law's status at every edge of a block's grammar, PIL's bytes where it is
+    0, and the model equal to the law at sizes that cut the 8 .. 17 bytes of these units.  video.jpeg_parse and the library accept a DC
+    table that lists the symbol 16, so dc_symbol_16 runs like the others."""
+    data = D.edge_stream(name)
+    p = D.parse(data)
+    assert (p.height, p.width, len(p.comps), len(p.units)) == (8, 16, 1, 1) and 8 <= len(p.units[0]) <= 17
+    rgb, status = D.decode(data)
+    assert status == D.EDGE_BLOCKS[name][1]
+    if status == D.OK:
+        assert np.array_equal(rgb, D.pil_decode(data))
+        first, second = law(data)[0][0][0]
+        assert first[63] == (-3 if name == "coefficient_63_no_eob" else 0) and list(second[[0, 1, 9]]) == [8, 4, -9]
+    hold(data, (1, 2, 4, 64), status=D.EDGE_BLOCKS[name][1])
+
+
 def test_the_fixtures_stress_what_they_are_named_for():
     worst = D.pil_jpeg(D.images(17, 33)[2], 100, 2)
     seen = hold(worst, (2, 4))
@@ -111,7 +128,7 @@ def test_the_fixtures_stress_what_they_are_named_for():
 
 def test_a_real_frame_synchronises_in_a_few_rounds():
     """480 x 640 at 4:2:0, quality 90, no restart intervals: the rounds and every subsequence's entry state are held to ONE continuing
-    walk of the same model (the law's own walk takes minutes at this size; the GPU test holds the pixels to the one-lane path)."""
+    walk of the same model (the law's own walk takes minutes at this size; the GPU test holds the pixels to PIL)."""
     p = D.parse(D.pil_jpeg(M.smooth_frames(1)[0], 90, 2))
     scan, unit = R.Scan(p), R.Unit(p.units[0])
     rounds, subs = R.synchronise(scan, unit, 128)

@@ -5,15 +5,16 @@ before it had a decoder: PIL on one host thread plus the upload.
     python tools/decode_bench.py [--frames 90] [--repeats 3] [--chunks 8,32] [--kernels] [--splits 32,64,128,256]
     python tools/decode_bench.py --rounds [--splits 32,64,128,256]      (no GPU: the host model's convergence figures)
 
-Three classes of stream (MEASUREMENTS.md, "JPEG decode"):
+Four classes of stream (MEASUREMENTS.md, "JPEG decode"):
   (a) the package's own files, video.jpeg_encode at quality 90: 480 x 2560 visualisation rows and 480 x 640 frames (4:4:4, one MCU row
       per restart interval);
   (b) PIL 480 x 640 quality-90 4:2:0 files without restart intervals;
-  (c) the same with restart_marker_rows=1.
-Per class and chunk: frames/s of video.jpeg_decode (parse + upload + kernels, synchronised at the end), `--repeats` times; frames/s of
-PIL + upload, as often; the bytes that cross PCIe and the bytes the kernels move; then the same call with entropy="split" (the
-entropy launch that cuts a unit into subsequences which synchronise themselves) at the default subsequence size, and at every size of
-`--splits` for the largest chunk.  `--kernels` adds the device time of every launch of one call, from torch.profiler's kernel records.
+  (c) the same with restart_marker_rows=1;
+  (d) the same with restart_marker_blocks=1 and =5: units of one or a few subsequences, 1 200 and 240 of them per frame.
+Per class and chunk: frames/s of video.jpeg_decode (parse + upload + kernels, synchronised at the end), `--repeats` times behind one
+untimed call; frames/s of PIL + upload, as often; the bytes that cross PCIe and the bytes the kernels move; then the same call at
+every subsequence size of `--splits` for the largest chunk.  `--kernels` adds the device time of every launch of one call, from
+torch.profiler's kernel records.
 `--rounds` runs nowhere near a GPU: per class it prints the subsequences and the synchronisation rounds of the longest unit of the
 first file under tests/jpeg_split_ref.py, the scheme's host model (class (a) is then written by tests/mjpeg_ref.py, the encoder's law,
 whose bytes are the package's own).  One JSON object per line."""
@@ -72,7 +73,9 @@ def classes(n, host_only=False):
         own = video.jpeg_encode(torch.from_numpy(base).cuda(), 90)
         rows = video.jpeg_encode(torch.from_numpy(np.concatenate([base[:3]] * 4, 2)).cuda(), 90)
     return {"a_rows_480x2560": [rows[k % len(rows)] for k in range(n)], "a_frames_480x640": [own[k % len(own)] for k in range(n)],
-            "b_pil_420_no_restart": pil_files(frames), "c_pil_420_restart_rows": pil_files(frames, restart_marker_rows=1)}
+            "b_pil_420_no_restart": pil_files(frames), "c_pil_420_restart_rows": pil_files(frames, restart_marker_rows=1),
+            "d_pil_420_restart_1_mcu": pil_files(frames, restart_marker_blocks=1),
+            "d_pil_420_restart_5_mcus": pil_files(frames, restart_marker_blocks=5)}
 
 
 def time_gpu(jpegs, chunk, **how):
@@ -138,7 +141,7 @@ def main():
     ap.add_argument("--splits", default="32,64,128,256", help="subsequence sizes of the split path to sweep at the largest chunk")
     ap.add_argument("--rounds", action="store_true", help="no GPU: subsequences and rounds per class from the host model")
     args = ap.parse_args()
-    splits = [int(v) for v in args.splits.split(",")]
+    splits = [int(v) for v in args.splits.split(",") if v]
     if args.rounds:
         return rounds(splits)
     from articulation3d_amd import opt_ops, video
@@ -157,19 +160,17 @@ def main():
                "bytes_per_frame": {"h2d": round(scan), "coef_memset": 2 * ce, "coef_read": 2 * ce, "planes_write_read": 2 * pe, "rgb_write": rgb,
                                    "pil_path_h2d": rgb}}
         chunks = [int(c) for c in args.chunks.split(",")]
-        time_gpu(jpegs[:4], 4, entropy="split")
         for chunk in chunks:
-            for key, how in (("gpu", {}), ("split", {"entropy": "split"})):
-                runs = [time_gpu(jpegs, chunk, **how) for _ in range(args.repeats)]
-                assert torch.equal(runs[0][1][:4], want), f"the GPU decoder ({key}) and PIL disagree"
-                row[f"{key}_fps_chunk{chunk}"] = [round(r[0], 1) for r in runs]
-                if args.kernels:
-                    try:
-                        row[f"{key}_kernel_us_chunk{chunk}"] = kernel_times(jpegs, chunk, **how)
-                    except Exception as e:  # a profiler that is not there is not a failed measurement
-                        row[f"{key}_kernel_us_chunk{chunk}"] = f"unavailable: {type(e).__name__}: {e}"
+            # an untimed call first: the scratch and the output of this chunk size come from the allocator's blocks afterwards
+            assert torch.equal(time_gpu(jpegs, chunk)[1][:4], want), "the GPU decoder and PIL disagree"
+            row[f"gpu_fps_chunk{chunk}"] = [round(time_gpu(jpegs, chunk)[0], 1) for _ in range(args.repeats)]
+            if args.kernels:
+                try:
+                    row[f"gpu_kernel_us_chunk{chunk}"] = kernel_times(jpegs, chunk)
+                except Exception as e:  # a profiler that is not there is not a failed measurement
+                    row[f"gpu_kernel_us_chunk{chunk}"] = f"unavailable: {type(e).__name__}: {e}"
         for split in splits:  # the sweep the default subsequence size is taken from, at the largest chunk
-            how = {"entropy": "split", "split_bytes": split}
+            how = {"split_bytes": split}
             runs = [time_gpu(jpegs, max(chunks), **how) for _ in range(args.repeats)]
             assert torch.equal(runs[0][1][:4], want), f"the GPU decoder (split {split}) and PIL disagree"
             row[f"split{split}_fps_chunk{max(chunks)}"] = [round(r[0], 1) for r in runs]

@@ -16,7 +16,7 @@ Input (this image has no H.264 decoder: cv2 / imageio are absent, so .mp4 / .mov
   * a directory of .png / .jpg frames, sorted by name: baseline JPEG files of one size go through the same GPU decoder, everything
     else (PNG, progressive or otherwise refused files, frames the decoder flags) through PIL -- `--decoder auto|gpu|pil`, the frames
     are the same bytes under all three: `gpu` and `auto` send every baseline stream to the GPU, with restart intervals or without
-    (a scan without them is split among many lanes that synchronise themselves: jpeg_decode's entropy="split"), `pil` none, or
+    (a scan without them is split among many lanes that synchronise themselves), `pil` none, or
   * `synthetic:N` / `synthetic:NxHxW` -- N seeded random frames (plumbing check), optionally at a source size H x W.
 The frames go to the GPU as they come from the reader (uint8 RGB, any size): the reference's `cv2.resize(im, (640, 480))` and
 BGR flip (:216-218) run on the device, fused with the normalisation in front of the stem (a3d_preprocess_resize_u8).
@@ -95,8 +95,8 @@ def decode_images(blobs, decoder: str = "auto") -> np.ndarray:
             if gpu_decodes(info, decoder) and geometry in (None, info.geometry):
                 geometry = info.geometry
                 chosen.append(k)
-        if chosen:  # the entropy launch that splits a unit among lanes: the same bytes, faster with and without restart intervals (MEASUREMENTS.md)
-            out, status = jpeg_decode([blobs[k] for k in chosen], chunk=32, strict=False, entropy="split")
+        if chosen:
+            out, status = jpeg_decode([blobs[k] for k in chosen], chunk=32, strict=False)
             out = out.cpu().numpy()
             for i, k in enumerate(chosen):
                 if int(status[i]) == 0:
