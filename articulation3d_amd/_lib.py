@@ -289,6 +289,7 @@ class MeshDesc(C.Structure):
 
 JPEG_BLOCK_BITS, JPEG_HUFF_VALS = 1658, 162
 JPEG_RANGE, JPEG_BAD_CODE, JPEG_SHORT, JPEG_TABSET_BYTES, JPEG_SPLIT_BYTES = 1, 2, 3, 192 + 6 * (16 + 256), 32
+PNG_MAX_W, PNG_SEG_BYTES, PNG_SYMS, PNG_HDR_AT, PNG_TAB_WORDS = 5461, 8192, 316, 320, 400
 
 
 class JpegDecodeDesc(C.Structure):
@@ -448,6 +449,10 @@ SIGNATURES = {
     "a3d_jpeg_decode_scratch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "a3d_jpeg_decode": (C.c_int, [C.POINTER(JpegDecodeDesc), fptr]),
     "a3d_jpeg_decode_split": (C.c_int, [C.POINTER(JpegDecodeDesc), C.c_int, fptr]),
+    "a3d_png_slot_bytes": (C.c_size_t, [C.c_int]),
+    "a3d_png_scan": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr]),
+    "a3d_png_emit": (C.c_int, [fptr, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr]),
+    "a3d_png_pack": (C.c_int, [fptr, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, C.c_longlong, fptr]),
     "a3d_sgd_momentum": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_sgd_momentum_bf16g": (C.c_int, [fptr, fptr, fptr, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fptr]),
     "a3d_f32_to_bf16_scaled": (C.c_int, [fptr, fptr, C.c_size_t, C.c_float, fptr]),

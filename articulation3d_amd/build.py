@@ -55,6 +55,7 @@ SOURCES = {
     "plane_eval.hip": ["-ffp-contract=off"],  # box IoU and compare_planes round like tests/plane_eval_ref.py's separate float64 operators
     "jpeg.hip": [],  # integers only: nothing to contract
     "jpeg_decode.hip": [],  # integers only
+    "png.hip": [],  # integers only
 }
 COMMON =["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 COMMON += os.environ.get("A3D_HIPCC_FLAGS", "").split()  # developer builds only (e.g. -DA3D_ABLATIONS: timing-only kernel variants)

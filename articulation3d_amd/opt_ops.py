@@ -345,3 +345,46 @@ def jpeg_decode_into(rgb: torch.Tensor, status: torch.Tensor, data: torch.Tensor
         _lib.check(_lib.lib().a3d_jpeg_decode(C.byref(d), _stream()), "a3d_jpeg_decode")
     else:
         _lib.check(_lib.lib().a3d_jpeg_decode_split(C.byref(d), int(split_bytes), _stream()), "a3d_jpeg_decode_split")
+
+
+def png_geometry(H: int, W: int):
+    """(bytes of a filtered row, rows per segment, segments per frame, bytes of a segment's slot) of a3d_png_scan for H x W frames."""
+    from .png import geometry
+
+    stride, R, S = geometry(int(H), int(W))  # ValueError outside 1 .. 65535 rows of 1 .. PNG_MAX_W pixels
+    return stride, R, S, int(_lib.lib().a3d_png_slot_bytes(int(W)))
+
+
+def png_scan_into(frames_u8: torch.Tensor, filt: torch.Tensor, tok: torch.Tensor, hist: torch.Tensor, s1: torch.Tensor, s2: torch.Tensor) -> None:
+    """a3d_png_scan into caller-owned buffers (no synchronisation): filt uint8 and tok int16 (the library's uint16) of at least F*H*stride
+    elements, hist int32 [>= F*316], s1 int32 and s2 int64 (the library's unsigned words) [>= F*S]."""
+    F_, H, W, pitch = _pitched_frames(frames_u8)
+    stride, _R, S, _slot = png_geometry(H, W)
+    if (_req(filt, torch.uint8).numel() < F_ * H * stride or _req(tok, torch.int16).numel() < F_ * H * stride
+            or _req(hist, torch.int32).numel() < F_ * _lib.PNG_SYMS or _req(s1, torch.int32).numel() < F_ * S or _req(s2, torch.int64).numel() < F_ * S):
+        raise ValueError("a buffer of a3d_png_scan is smaller than the call needs")
+    _lib.check(_lib.lib().a3d_png_scan(_p(frames_u8), F_, H, W, pitch, _p(filt), _p(tok), _p(hist), _p(s1), _p(s2), _stream()), "a3d_png_scan")
+
+
+def png_emit_into(filt: torch.Tensor, tok: torch.Tensor, tab: torch.Tensor, F_: int, H: int, W: int, slots: torch.Tensor, seg_len: torch.Tensor,
+                  seg_off: torch.Tensor, frame_off: torch.Tensor, kind: torch.Tensor) -> None:
+    """a3d_png_emit: tab int32 [>= F*PNG_TAB_WORDS] holds every frame's code table and block header (png.frame_table); slots uint8
+    [>= F*S*slot], seg_len / seg_off / kind int32 [>= F*S], frame_off int32 [>= F+1]."""
+    stride, _R, S, slot = png_geometry(H, W)
+    F_ = int(F_)
+    if (_req(filt, torch.uint8).numel() < F_ * H * stride or _req(tok, torch.int16).numel() < F_ * H * stride
+            or _req(tab, torch.int32).numel() < F_ * _lib.PNG_TAB_WORDS or _req(slots, torch.uint8).numel() < F_ * S * slot
+            or _req(seg_len, torch.int32).numel() < F_ * S or _req(seg_off, torch.int32).numel() < F_ * S or _req(kind, torch.int32).numel() < F_ * S
+            or _req(frame_off, torch.int32).numel() < F_ + 1):
+        raise ValueError("a buffer of a3d_png_emit is smaller than the call needs")
+    _lib.check(_lib.lib().a3d_png_emit(_p(filt), _p(tok), _p(tab), F_, H, W, _p(slots), _p(seg_len), _p(seg_off), _p(frame_off), _p(kind), _stream()),
+               "a3d_png_emit")
+
+
+def png_pack_into(slots: torch.Tensor, seg_off: torch.Tensor, seg_len: torch.Tensor, F_: int, H: int, W: int, packed: torch.Tensor) -> None:
+    """a3d_png_pack: every segment to its place in `packed` (uint8, frame_off[F] bytes or more)."""
+    _stride, _R, S, slot = png_geometry(H, W)
+    if _req(slots, torch.uint8).numel() < F_ * S * slot or _req(seg_off, torch.int32).numel() < F_ * S or _req(seg_len, torch.int32).numel() < F_ * S:
+        raise ValueError("a buffer of a3d_png_pack is smaller than the call needs")
+    _lib.check(_lib.lib().a3d_png_pack(_p(slots), _p(seg_off), _p(seg_len), int(F_), H, W, _p(_req(packed, torch.uint8)), packed.numel(), _stream()),
+               "a3d_png_pack")

@@ -1273,6 +1273,68 @@ int a3d_jpeg_decode(const a3d_jpeg_decode_desc *d, void *stream);
  * A3D_ERR_ARG cases, status codes and result; split_bytes < 1 is A3D_ERR_ARG as well. */
 int a3d_jpeg_decode_split(const a3d_jpeg_decode_desc *d, int split_bytes, void *stream);
 
+/* ================================================================================================
+ * PNG: the lossless sibling of the Motion-JPEG writer (articulation3d_amd/png.py).  uint8 [F,H,pitch,3] RGB frames on the device ->
+ * per frame the deflate blocks of one zlib stream: filtering, LZ77 and Huffman coding run on the device, the host builds each
+ * frame's Huffman code from a histogram the device leaves and writes the container (signature, IHDR, one IDAT = 78 01 | the packed
+ * segments | 03 00 | Adler-32, IEND, the chunk CRCs).  8-bit truecolour, no interlace.  Integer arithmetic only.
+ *
+ * The law (held byte for byte by tests/png_ref.py, which tests/test_png_host.py holds to zlib's inflate and to PIL):
+ *   filter    stride = 1 + 3 W bytes per filtered row: the filter type, then the filtered samples (bpp = 3).  With x the byte, a the
+ *             byte 3 to its left, b the byte above, c the byte above a (bytes outside the image are 0; the row above row 0 is zeros):
+ *             0 None x, 1 Sub x - a, 2 Up x - b, 3 Average x - floor((a + b) / 2), 4 Paeth x - P(a, b, c) with the standard
+ *             predictor (p = a + b - c; the nearest of a, b, c to p, ties in that order), all modulo 256.  A row takes the type
+ *             whose filtered samples have the smallest sum of (v < 128 ? v : 256 - v); ties go to the lowest type.
+ *   segments  a frame's H * stride filtered bytes are cut into segments of R = max(1, ceil(8192 / stride)) whole rows, the last one
+ *             possibly shorter: S = ceil(H / R) segments of n <= 16384 bytes (W <= A3D_PNG_MAX_W, so that stride <= 16384).  One
+ *             workgroup codes one segment.
+ *   tokens    at byte i of a segment (g = its index in the frame) the candidate distances are d = 1, 3 and stride.  A candidate
+ *             needs g - d >= 0: its source may lie in the segment before.  L_d(i) = the number of k = 0, 1, ... with
+ *             f[g + k] == f[g + k - d], counted up to the first failure, capped at 258 and at n - i.  The candidate with the longest
+ *             L wins, ties go to the smallest d.  L >= 3: a match (L, d), i += L; otherwise the literal f[g], i += 1.  Greedy from
+ *             i = 0, no lazy matching.  (On the device L_d is a bit scan over equality masks, and the token starts are found by
+ *             pointer doubling over next[i]: after round r the first 2^(r+1) tokens are marked.)
+ *   symbols   RFC 1951's: literals 0 .. 255, end of block 256, lengths 257 .. 285 and distances 0 .. 29 with their extra bits.
+ *   histogram per frame 286 literal / length counts and 30 distance counts over the tokens of all its segments, plus one end of
+ *             block per segment.  The host turns it into the frame's code (articulation3d_amd/png.py: huffman_lengths,
+ *             dynamic_header) and hands back a table of A3D_PNG_TAB_WORDS words per frame: words 0 .. 315 the symbols' codes as
+ *             (bit-reversed code | length << 16), literal / length first; word 316 the bits of the block header; from word
+ *             A3D_PNG_HDR_AT the header as a bit string, LSB first, starting with BFINAL = 0, BTYPE = 10, zero past its end.
+ *   coding    a segment takes the cheapest in bytes of (ties go to the lowest number)
+ *               0 stored   00 | LEN | NLEN | the n bytes: n + 5 bytes
+ *               1 fixed    BFINAL 0, BTYPE 01, the tokens in the fixed code, end of block, then an empty stored block
+ *               2 dynamic  the frame's header, the tokens in the frame's code, end of block, then an empty stored block
+ *             where the empty stored block is 000, zero bits up to a byte boundary, 00 00 FF FF (a sync flush).  So every segment
+ *             ends on a byte boundary, segments concatenate as bytes, and no segment takes more than n + 5 bytes.  Bits are
+ *             packed LSB first, Huffman codes most significant bit first, extra bits as integers (RFC 1951, 3.1.1).
+ *   Adler     per segment s1 = sum of b_k (uint32) and s2 = sum of (n - k) b_k (uint64), k = 0 .. n - 1: the host folds them.
+ *   stream    frame f's deflate data is packed[frame_off[f] .. frame_off[f+1]), its segments in order.
+ * The result of a frame does not depend on F or on the frames beside it.
+ * ============================================================================================== */
+#define A3D_PNG_MAX_W 5461
+#define A3D_PNG_SEG_BYTES 8192 /* a segment is the fewest whole rows that reach this many filtered bytes */
+#define A3D_PNG_SYMS 316       /* 286 literal / length + 30 distance */
+#define A3D_PNG_HDR_AT 320
+#define A3D_PNG_TAB_WORDS 400  /* a dynamic header is at most 17 + 19 * 3 + 316 * 7 = 2286 bits */
+/* Bytes of one segment's slot for frames W wide: the largest segment + 5, rounded up to 16; 0 for W outside 1 .. A3D_PNG_MAX_W. */
+size_t a3d_png_slot_bytes(int W);
+/* frames uint8 [F,H,pitch,3] -> filt [F][H*stride] the filtered bytes; tok uint16 [F][H*stride]: 0 where no token starts, else
+ * L | (0, 1, 2 for d = 1, 3, stride) << 9 with L = 1 for a literal; hist int32 [F][A3D_PNG_SYMS]; s1 uint32 [F*S], s2 uint64 [F*S].
+ * One memset and two launches, no synchronisation.  A3D_ERR_ARG before any launch: F < 0, H outside 1 .. 65535, W outside
+ * 1 .. A3D_PNG_MAX_W, pitch < W, a null pointer with F > 0, or F * H * stride or F * S * slot_bytes above 2^31 - 1. */
+int a3d_png_scan(const unsigned char *frames, int F, int H, int W, int pitch, unsigned char *filt, unsigned short *tok, int *hist,
+                 unsigned int *s1, unsigned long long *s2, void *stream);
+/* filt, tok of a3d_png_scan and tab uint32 [F][A3D_PNG_TAB_WORDS] (device) -> every segment coded at slots + s * slot_bytes, seg_len
+ * [F*S] its bytes, kind [F*S] its coding, seg_off [F*S] its place in the packed stream, frame_off [F+1].  Two launches.  The kernel
+ * clamps what it finds in tab (a length to 15 bits, the header to its words), so no table can make a write leave a slot.
+ * A3D_ERR_ARG as a3d_png_scan (frame_off always non-null). */
+int a3d_png_emit(const unsigned char *filt, const unsigned short *tok, const unsigned int *tab, int F, int H, int W,
+                 unsigned char *slots, int *seg_len, int *seg_off, int *frame_off, int *kind, void *stream);
+/* Copies every segment to packed + seg_off[s].  packed_bytes is the size of the destination (the host reads frame_off[F] first): a
+ * segment that would end past it is left out, never written.  F == 0 is a no-op. */
+int a3d_png_pack(const unsigned char *slots, const int *seg_off, const int *seg_len, int F, int H, int W, unsigned char *packed,
+                 long long packed_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,9 @@ translation axis, RLE mask) and <output>/tracks.json (tracked planes, has_rot, c
 <output>/vis/frame_%05d.png, one <output>/vis.npy, or the video <output>/output.avi.  The video is Motion-JPEG in an AVI container,
 not the reference's H.264 .mp4: every frame is a baseline JPEG (4:4:4, `--vis-quality`), encoded on the GPU
 (articulation3d_amd/video.py), played at `--fps` (a .npy or an image directory carries no frame rate; the reference takes its reader's).
+The .png files are lossless either way: `--png-encoder gpu` filters, matches and Huffman-codes the rows on the GPU
+(articulation3d_amd/png.py) and only compressed bytes come to the host, `pil` brings the rows to the host for PIL's zlib, `auto` (the
+default) takes the faster one, the GPU; the two write different bytes that decode to the same pixels.
 `--save-obj` writes the reference's 3-D model (its save_obj_model, :44-168) for the frames of `--obj-frames`:
 <output>/frame_%04d/arti_pred.obj + .mtl + uv_maps/*.png -- the most confident articulated plane in its opened poses, two axis
 markers and the background, as dense meshes built on the GPU (articulation3d_amd/mesh.py states the departures).
@@ -175,6 +178,19 @@ def snapshot_predictions(preds):
     return out
 
 
+PNG_AUTO_GPU = True  # MEASUREMENTS.md, "PNG encode": render_clip_png against render_clip + PIL, end to end
+
+
+def png_on_gpu(choice: str, device, width: int) -> bool:
+    """Whether `--vis png` rows of `width` pixels are encoded on the GPU (articulation3d_amd/png.py).  `gpu`: always (a row the encoder
+    refuses is an error); `pil`: never; `auto`: on a CUDA device, for rows the encoder takes, if it was measured faster end to end."""
+    from articulation3d_amd.png import MAX_W
+
+    if choice == "auto":
+        return PNG_AUTO_GPU and torch.device(device).type == "cuda" and width <= MAX_W
+    return choice == "gpu"
+
+
 def write_visualisation(args, device, frames_rgb, raw_preds, opt_preds, chunk: int = 32):
     """--vis: resize the clip's frames on the device in chunks of `chunk` source frames (the detector's own front end, uint8
     output, 0.9 MB per resized frame kept on the device), then ONE render_clip over the whole clip: its buffers are pinned and
@@ -193,6 +209,16 @@ def write_visualisation(args, device, frames_rgb, raw_preds, opt_preds, chunk: i
         from PIL import Image
 
         os.makedirs(os.path.join(args.output, "vis"), exist_ok=True)
+        if png_on_gpu(args.png_encoder, device, 4 * 640):
+            from articulation3d_amd.png import render_clip_png
+
+            at = 0
+            for pngs in render_clip_png(u8, raw_preds, opt_preds, chunk=8, mask_alpha=args.mask_alpha, conf_threshold=args.conf_threshold):
+                for png in pngs:
+                    with open(os.path.join(args.output, "vis", "frame_%05d.png" % at), "wb") as f:
+                        f.write(png)
+                    at += 1
+            return
     elif args.vis == "npy":
         whole = np.lib.format.open_memmap(os.path.join(args.output, "vis.npy"), mode="w+", dtype=np.uint8, shape=(n, 480, 4 * 640, 3))
     if args.vis == "avi":
@@ -269,6 +295,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--decoder", choices=("auto", "gpu", "pil"), default="auto",
                     help="who decodes JPEG input (.avi chunks, .jpg files): gpu = every baseline stream on the GPU, pil = PIL on the host, auto = "
                          "the GPU for the streams it was measured to decode faster (every baseline stream, with restart intervals or without); the frames are the same bytes")
+    ap.add_argument("--png-encoder", choices=("auto", "gpu", "pil"), default="auto",
+                    help="who writes the --vis png files: gpu = filtering, LZ77 and Huffman coding on the GPU, only compressed bytes come to the "
+                         "host; pil = the rows come to the host and PIL's zlib compresses them; auto = the GPU where it was measured faster "
+                         "(MEASUREMENTS.md, 'PNG encode').  The files differ in bytes and decode to the same pixels")
     ap.add_argument("--mask-alpha", default=0.0, type=float,
                     help="--vis: opacity of the instance masks on the seg panels (0 = none, as the reference draws them)")
     ap.add_argument("--save-obj", action="store_true",
