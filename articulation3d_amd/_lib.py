@@ -290,6 +290,7 @@ class MeshDesc(C.Structure):
 JPEG_BLOCK_BITS, JPEG_HUFF_VALS = 1658, 162
 JPEG_RANGE, JPEG_BAD_CODE, JPEG_SHORT, JPEG_TABSET_BYTES, JPEG_SPLIT_BYTES = 1, 2, 3, 192 + 6 * (16 + 256), 32
 PNG_MAX_W, PNG_SEG_BYTES, PNG_SYMS, PNG_HDR_AT, PNG_TAB_WORDS = 5461, 8192, 316, 320, 400
+PNGD_SHORT, PNGD_BAD_CODE, PNGD_FAR, PNGD_LONG, PNGD_FILTER, PNGD_ADLER = 1, 2, 3, 4, 5, 6
 
 
 class JpegDecodeDesc(C.Structure):
@@ -300,6 +301,16 @@ class JpegDecodeDesc(C.Structure):
         ("sets", C.POINTER(C.c_ubyte)),
         ("d_data", fptr), ("d_meta", fptr), ("d_sets", fptr), ("coef", fptr), ("planes", fptr), ("rgb", fptr), ("status", fptr),
     ]
+
+
+class PngDecodeDesc(C.Structure):
+    _fields_ = [
+        ("F", C.c_int), ("H", C.c_int), ("W", C.c_int), ("pitch", C.c_int), ("channels", C.c_int), ("data_bytes", C.c_longlong),
+        ("frame_off", C.POINTER(C.c_int)),
+        ("d_data", fptr), ("d_frame_off", fptr), ("raw", fptr), ("rgb", fptr), ("status", fptr),
+    ]
+
+
 EVAL_DET_COLS, EVAL_GT_FCOLS, EVAL_GT_ICOLS, EVAL_MAX_GT, EVAL_MAX_CLASSES = 14, 7, 12, 64, 64
 
 
@@ -449,6 +460,8 @@ SIGNATURES = {
     "a3d_jpeg_decode_scratch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "a3d_jpeg_decode": (C.c_int, [C.POINTER(JpegDecodeDesc), fptr]),
     "a3d_jpeg_decode_split": (C.c_int, [C.POINTER(JpegDecodeDesc), C.c_int, fptr]),
+    "a3d_png_decode_scratch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "a3d_png_decode": (C.c_int, [C.POINTER(PngDecodeDesc), fptr]),
     "a3d_png_slot_bytes": (C.c_size_t, [C.c_int]),
     "a3d_png_scan": (C.c_int, [fptr, C.c_int, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr]),
     "a3d_png_emit": (C.c_int, [fptr, fptr, fptr, C.c_int, C.c_int, C.c_int, fptr, fptr, fptr, fptr, fptr, fptr]),

@@ -56,6 +56,7 @@ SOURCES = {
     "jpeg.hip": [],  # integers only: nothing to contract
     "jpeg_decode.hip": [],  # integers only
     "png.hip": [],  # integers only
+    "png_decode.hip": [],  # integers only
 }
 COMMON =["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 COMMON += os.environ.get("A3D_HIPCC_FLAGS", "").split()  # developer builds only (e.g. -DA3D_ABLATIONS: timing-only kernel variants)

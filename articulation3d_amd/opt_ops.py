@@ -388,3 +388,32 @@ def png_pack_into(slots: torch.Tensor, seg_off: torch.Tensor, seg_len: torch.Ten
         raise ValueError("a buffer of a3d_png_pack is smaller than the call needs")
     _lib.check(_lib.lib().a3d_png_pack(_p(slots), _p(seg_off), _p(seg_len), int(F_), H, W, _p(_req(packed, torch.uint8)), packed.numel(), _stream()),
                "a3d_png_pack")
+
+
+def png_decode_scratch(H: int, W: int, channels: int) -> int:
+    """Bytes of `raw` scratch that a3d_png_decode needs PER FRAME of this geometry."""
+    n = C.c_size_t()
+    if _lib.lib().a3d_png_decode_scratch(int(H), int(W), int(channels), C.byref(n)) != 0:
+        raise ValueError(f"{H} x {W}, {channels} channel(s): outside the PNG decoder's law")
+    return int(n.value)
+
+
+def png_decode_into(rgb: torch.Tensor, status: torch.Tensor, data: torch.Tensor, frame_off, frame_off_dev: torch.Tensor, channels: int,
+                    raw: torch.Tensor) -> None:
+    """a3d_png_decode into caller-owned buffers (no synchronisation).  rgb uint8 [F,H,W,3] on the device (dense or a column range of
+    wider rows), status int32 [F]; data uint8 on the device, a multiple of 4 bytes holding the frames' deflate bodies back to back;
+    frame_off a contiguous int32 numpy array [F+1] with its device copy; raw scratch of F x png_decode_scratch bytes."""
+    import numpy as np
+
+    F_, H, W, pitch = _pitched_frames(rgb)
+    per = png_decode_scratch(H, W, channels)
+    frame_off = np.ascontiguousarray(frame_off, np.int32)
+    total = int(frame_off[-1]) if frame_off.size else 0
+    if (frame_off.size != F_ + 1 or _req(frame_off_dev, torch.int32).numel() < F_ + 1 or _req(data, torch.uint8).numel() < (total + 3) // 4 * 4
+            or _req(raw, torch.uint8).numel() < F_ * per or _req(status, torch.int32).numel() < F_):
+        raise ValueError("a buffer of a3d_png_decode is smaller than the call needs")
+    d = _lib.PngDecodeDesc()
+    d.F, d.H, d.W, d.pitch, d.channels, d.data_bytes = F_, H, W, pitch, int(channels), total
+    d.frame_off = C.cast(frame_off.ctypes.data, C.POINTER(C.c_int))
+    d.d_data, d.d_frame_off, d.raw, d.rgb, d.status = _p(data), _p(frame_off_dev), _p(raw), _p(rgb), _p(status)
+    _lib.check(_lib.lib().a3d_png_decode(C.byref(d), _stream()), "a3d_png_decode")

@@ -13,6 +13,7 @@ chunk CRCs and the container.  Only compressed bytes, 316 counts per frame and t
 """
 from __future__ import annotations
 
+import dataclasses
 import heapq
 import struct
 import time
@@ -367,3 +368,154 @@ def render_clip_png(frames_u8, preds_raw: Sequence, preds_opt: Sequence, chunk: 
         pending = enc[b]
     if pending is not None:
         yield finish(pending)
+
+
+# ---- reading ---------------------------------------------------------------------------------------------------------------------
+PNGD_STATUS = {_lib.PNGD_SHORT: "SHORT", _lib.PNGD_BAD_CODE: "BAD_CODE", _lib.PNGD_FAR: "FAR", _lib.PNGD_LONG: "LONG",
+               _lib.PNGD_FILTER: "FILTER", _lib.PNGD_ADLER: "ADLER"}
+_CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}
+DECODE_CHUNK = 90  # frames per a3d_png_decode call: the fastest of 8, 32 and 90 for four of five classes of file (MEASUREMENTS.md, "PNG decode")
+
+
+@dataclasses.dataclass(frozen=True)
+class PNGInfo:
+    """What png_parse finds: the geometry and where the deflate body lies -- the byte ranges (lo, hi) of the file whose concatenation
+    is the IDAT payload without the two bytes of the zlib header (the Adler-32 at its end included)."""
+    height: int
+    width: int
+    channels: int
+    ranges: tuple
+
+    @property
+    def geometry(self):
+        return self.height, self.width, self.channels
+
+    @property
+    def raw_size(self) -> int:
+        return self.height * (1 + self.width * self.channels)
+
+
+def png_parse(data: bytes) -> PNGInfo:
+    """The container of one PNG file, on the host: the chunk walk, every chunk's CRC, IHDR and the zlib header.  ValueError names
+    what puts a file outside the law of include/a3d.h ("PNG decode"): palette, bit depths other than 8, Adam7, a damaged container.
+    Ancillary chunks (tRNS included) are skipped."""
+    if data[:8] != SIGNATURE:
+        raise ValueError("not a PNG file (bad signature)")
+    at, n_data = 8, len(data)
+    ihdr, ranges, seen_idat, closed, ended = None, [], False, False, False
+    while at < n_data:
+        if at + 12 > n_data:
+            raise ValueError("chunk cut short")
+        n, kind = struct.unpack_from(">I4s", data, at)
+        if at + 12 + n > n_data:
+            raise ValueError(f"chunk {kind!r} cut short")
+        if zlib.crc32(data[at + 4:at + 8 + n]) != struct.unpack_from(">I", data, at + 8 + n)[0]:
+            raise ValueError(f"chunk {kind!r}: CRC does not match")
+        if ihdr is None and kind != b"IHDR":
+            raise ValueError("no IHDR chunk in front")
+        if kind == b"IHDR":
+            if ihdr is not None or n != 13:
+                raise ValueError("more than one IHDR chunk, or one of the wrong size")
+            ihdr = struct.unpack_from(">IIBBBBB", data, at + 8)
+        elif kind == b"IDAT":
+            if closed:
+                raise ValueError("IDAT chunks are not consecutive")
+            seen_idat = True
+            ranges.append((at + 8, at + 8 + n))
+        elif kind == b"IEND":
+            ended = True
+            break
+        if seen_idat and kind != b"IDAT":
+            closed = True
+        at += 12 + n
+    if ihdr is None:
+        raise ValueError("no IHDR chunk")
+    if not seen_idat:
+        raise ValueError("no IDAT chunk")
+    if not ended:
+        raise ValueError("no IEND chunk")
+    width, height, depth, colour, compression, filt, interlace = ihdr
+    if colour == 3:
+        raise ValueError("palette image (colour type 3)")
+    if colour not in _CHANNELS:
+        raise ValueError(f"colour type {colour}")
+    if depth != 8:
+        raise ValueError(f"bit depth {depth}: 8 only")
+    if interlace:
+        raise ValueError("interlaced (Adam7)")
+    if compression or filt:
+        raise ValueError(f"compression method {compression} / filter method {filt}")
+    if width == 0 or height == 0:
+        raise ValueError(f"{height} x {width}: an empty image")
+    channels = _CHANNELS[colour]
+    if height * (1 + width * channels) > 0x7FFFFFFF:
+        raise ValueError(f"{height} x {width} x {channels}: more than 2^31 - 1 bytes of rows")
+    head, body = [], []
+    for lo, hi in ranges:  # the zlib header may lie across chunks
+        take = min(2 - len(head), hi - lo)
+        head += data[lo:lo + take]
+        if hi > lo + take:
+            body.append((lo + take, hi))
+    if len(head) < 2:
+        raise ValueError("zlib header cut short")
+    cmf, flg = head
+    if cmf & 15 != 8 or cmf >> 4 > 7 or flg & 32 or (cmf << 8 | flg) % 31:
+        raise ValueError(f"zlib header {cmf:02x} {flg:02x}: want CM = 8, CINFO <= 7, FDICT = 0 and a valid FCHECK")
+    return PNGInfo(height, width, channels, tuple(body))
+
+
+def png_decode(pngs: Sequence[bytes], device="cuda", chunk: int = DECODE_CHUNK, strict: bool = True):
+    """F PNG files of one size and one colour type (8-bit grey, grey + alpha, RGB or RGBA, no interlace) -> uint8 [F,H,W,3] RGB on the
+    device, byte for byte PIL's Image.open(f).convert("RGB") (include/a3d.h states the law: grey is replicated, alpha dropped).  The host
+    walks the chunks and uploads the deflate bodies; inflate, Adler-32, unfiltering and the conversion run on the device, `chunk`
+    frames per a3d_png_decode call, and the host prepares a chunk while the device decodes the one before.  A frame's pixels do not
+    depend on the frames beside it or on `chunk`.  With `strict` a frame whose status is not 0 raises ValueError with its index and the
+    code (PNGD_STATUS); without, -> (frames, status int32 [F] on the host): the pixels of a flagged frame mean nothing."""
+    import torch
+
+    from . import opt_ops
+
+    infos = []
+    for i, blob in enumerate(pngs):
+        try:
+            infos.append(png_parse(blob))
+        except ValueError as e:
+            raise ValueError(f"frame {i}: {e}") from None
+    if not infos:
+        raise ValueError("png_decode: no frames")
+    for i, info in enumerate(infos):
+        if info.geometry != infos[0].geometry:
+            raise ValueError(f"frame {i} is {info.geometry} (H, W, channels), frame 0 is {infos[0].geometry}: one call decodes one geometry")
+    H, W, channels = infos[0].geometry
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"device {device!r}: the decoder runs on the GPU")
+    F = len(infos)
+    chunk = max(1, min(int(chunk), F))
+    per = opt_ops.png_decode_scratch(H, W, channels)
+    while chunk > 1 and chunk * per > 1 << 32:  # scratch of at most 4 GB
+        chunk = (chunk + 1) // 2
+    with torch.cuda.device(dev):
+        raw = torch.empty(chunk * per, dtype=torch.uint8, device=dev)
+        out = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+        status = torch.empty(F, dtype=torch.int32, device=dev)
+        for lo in range(0, F, chunk):
+            hi = min(lo + chunk, F)
+            pieces, off = [], [0]
+            for k in range(lo, hi):
+                pieces += [pngs[k][a:b] for a, b in infos[k].ranges]
+                off.append(off[-1] + sum(b - a for a, b in infos[k].ranges))
+            total = off[-1]
+            if total > 0x7FFFFFFF:
+                raise ValueError(f"frames {lo} .. {hi - 1} hold {total} bytes: more than one call takes, pass a smaller chunk")
+            blob = np.frombuffer(b"".join(pieces) + bytes(-total % 4 + 4), np.uint8)
+            off = np.array(off, np.int32)
+            opt_ops.png_decode_into(out[lo:hi], status[lo:hi], torch.from_numpy(blob.copy()).to(dev), off, torch.from_numpy(off).to(dev), channels, raw)
+        st = status.cpu()
+    if not strict:
+        return out, st
+    bad = torch.nonzero(st).flatten().tolist()
+    if bad:
+        raise ValueError(f"frame {bad[0]}: status {PNGD_STATUS.get(int(st[bad[0]]), int(st[bad[0]]))}" +
+                         (f" (and {len(bad) - 1} more frames)" if len(bad) > 1 else ""))
+    return out

@@ -1335,6 +1335,76 @@ int a3d_png_emit(const unsigned char *filt, const unsigned short *tok, const uns
 int a3d_png_pack(const unsigned char *slots, const int *seg_off, const int *seg_len, int F, int H, int W, unsigned char *packed,
                  long long packed_bytes, void *stream);
 
+/* ================================================================================================
+ * PNG decode: the deflate bodies of F PNG frames of one geometry -> uint8 [F,H,pitch,3] RGB on the device, byte for byte PIL's
+ * Image.open(f).convert("RGB").  The host (articulation3d_amd/png.py: png_parse) walks the chunks, checks every CRC, IHDR and the zlib
+ * header and refuses what is outside the law; inflate, the Adler-32, unfiltering and the conversion run on the device.  Integers only.
+ *
+ * The law (held byte for byte by tests/png_decode_ref.py, which tests/test_png_decode_host.py holds to zlib's inflate and to PIL):
+ *   accepted  bit depth 8; colour type 0, 2, 4 or 6 (1, 3, 2 or 4 channels); interlace 0, compression 0, filter method 0.  Grey is
+ *             replicated to R = G = B, an alpha channel is dropped, tRNS and every other ancillary chunk are ignored.  The host
+ *             refuses: palette, bit depths 1, 2, 4 and 16, Adam7, a bad signature, a chunk CRC that does not match, a missing IHDR,
+ *             IDAT or IEND, IDAT chunks that are not consecutive, a zlib header outside CM = 8, CINFO <= 7, FDICT = 0 with a valid
+ *             FCHECK, H or W of 0, a raw size H * (1 + W * channels) above 2^31 - 1.
+ *   body      a frame's bytes are its IDAT payloads concatenated, without the two bytes of the zlib header: deflate blocks, then,
+ *             byte-aligned behind the final block, the Adler-32 of the raw bytes, big-endian.  Anything behind it is ignored.
+ *   inflate   RFC 1951 in full: stored, fixed and dynamic blocks, any number of them; distances up to 32 768 whatever CINFO says;
+ *             out[p + k] = out[p - d + k mod d] for a copy of a length above its distance d.  A set of code lengths is illegal when
+ *             it is over-subscribed, or incomplete with a code longer than one bit (zlib's rule: one code of one bit, or none at all,
+ *             passes; a pattern such a set gives no code consumes one bit and is A3D_PNGD_BAD_CODE).  The code-length code itself must
+ *             be complete.  A code is consumed only if all its bits lie inside the stream; so are extra bits and header fields.
+ *   unfilter  per row of 1 + W * channels raw bytes: the type, then the samples.  The filter distance is bpp = channels; a = the
+ *             sample bpp to the left, b = above, c = above a; neighbours outside the image are 0; all arithmetic mod 256.
+ *             0 None x, 1 Sub x + a, 2 Up x + b, 3 Average x + floor((a + b) / 2) on the 9-bit sum, 4 Paeth x + P(a, b, c) with
+ *             p = a + b - c and the nearest of a, b, c to p, ties in that order.  A type above 4 counts as 0 and flags the frame.
+ *   status    per frame 0 or the FIRST thing that went wrong, in stream order, then the filter bytes, then the checksum:
+ *             A3D_PNGD_SHORT     bits needed past the stream's end (a stored block longer than the bytes left included); the final
+ *                                block ends before the raw size is reached; fewer than 4 bytes are left for the Adler-32.
+ *             A3D_PNGD_BAD_CODE  BTYPE 3; LEN != ~NLEN; HLIT above 286 or HDIST above 30; an illegal set of code lengths; no code
+ *                                for the end of block; literal / length symbol 286 or 287; distance symbol 30 or 31; repeat code 16
+ *                                with nothing before it; a repeat that runs past HLIT + HDIST.
+ *             A3D_PNGD_FAR       a distance that reaches before the first output byte (checked before the length).
+ *             A3D_PNGD_LONG      output that would pass the raw size (for a stored block: what the bytes left of it would
+ *                                write).  The walk stops there; nothing is written past the raw size.
+ *             A3D_PNGD_FILTER    a filter byte above 4.
+ *             A3D_PNGD_ADLER     the checksum differs from the four bytes where the walk ended.
+ *             The pixels of a flagged frame are outside the law.  Inside it: no stream content makes a read or a write leave the
+ *             buffers of the call or touch another frame's bytes, every loop is bounded by the stream's bit count or by the raw size,
+ *             and a frame's result does not depend on F or on the frames beside it.
+ *   scheme    inflate: one wave per frame.  The decode tables live in LDS (a 10-bit primary lookup for literal / length and for
+ *             distance codes; a longer code resolves through the first / count / offset rows of its length), built by all 64 lanes
+ *             from the block's code lengths.  One lane walks the codes and hands tokens over in batches of 64; all lanes place the
+ *             literals and run the batch's copies in order, each copy lane-parallel, in an LDS ring of the last 32 768 bytes.
+ *             Adler-32: one workgroup per frame, a = 1 + sum b_j, b = N + sum (N - j) b_j mod 65521.  unfilter + convert: one wave per
+ *             frame, bands of 64 rows in sequence; lane r owns row r of a band and reconstructs pixel t - r at step t, b and c come
+ *             from lane r - 1 by a cross-lane move; only the row above a band is read back from memory.
+ * ============================================================================================== */
+#define A3D_PNGD_SHORT 1
+#define A3D_PNGD_BAD_CODE 2
+#define A3D_PNGD_FAR 3
+#define A3D_PNGD_LONG 4
+#define A3D_PNGD_FILTER 5
+#define A3D_PNGD_ADLER 6
+/* Bytes PER FRAME of the `raw` scratch of a3d_png_decode: the raw size rounded up to 16, then 16 bytes (the stored and the computed
+ * Adler-32).  A3D_ERR_ARG for a geometry outside the law. */
+int a3d_png_decode_scratch(int H, int W, int channels, size_t *raw_bytes);
+typedef struct {
+    int F, H, W, pitch;          /* rgb is [F,H,pitch,3], pitch >= W pixels per row                                          */
+    int channels;                /* 1 grey, 2 grey + alpha, 3 RGB, 4 RGBA                                                    */
+    long long data_bytes;        /* the frames' bodies, back to back                                                         */
+    const int *frame_off;        /* HOST [F+1], read before any launch: frame f is bytes frame_off[f] .. frame_off[f+1]      */
+    const unsigned char *d_data; /* DEVICE: data_bytes rounded up to a multiple of 4 are readable; 4-byte aligned            */
+    const int *d_frame_off;      /* frame_off on the device                                                                  */
+    unsigned char *raw;          /* scratch, F * raw_bytes, 16-byte aligned                                                  */
+    unsigned char *rgb;          /* out; bytes of a row past W pixels are left alone                                         */
+    int *status;                 /* out [F]                                                                                  */
+} a3d_png_decode_desc;
+/* One memset and three launches (inflate, Adler-32, unfilter + convert) on the stream, no synchronisation.  The kernels clamp what
+ * they find in the device copy of the offsets.  A3D_ERR_ARG before any launch: a null pointer, a misaligned buffer, a geometry
+ * outside the law (channels outside 1 .. 4, H or W below 1, a raw size above 2^31 - 1), pitch < W, F outside 0 .. 65535, offsets that
+ * are not monotonic or do not start at 0 and end at data_bytes, or data_bytes above 2^31 - 1.  F == 0 is a no-op. */
+int a3d_png_decode(const a3d_png_decode_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

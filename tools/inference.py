@@ -13,10 +13,13 @@ Input (this image has no H.264 decoder: cv2 / imageio are absent, so .mp4 / .mov
   * a Motion-JPEG .avi (what `--vis avi` writes, and what cameras and ffmpeg -c:v mjpeg write): the frames are baseline JPEG, decoded
     on the GPU (articulation3d_amd/video.py: MJPEGReader + jpeg_decode) to the bytes PIL's libjpeg gives; `--fps` defaults to the
     container's rate, or
-  * a directory of .png / .jpg frames, sorted by name: baseline JPEG files of one size go through the same GPU decoder, everything
-    else (PNG, progressive or otherwise refused files, frames the decoder flags) through PIL -- `--decoder auto|gpu|pil`, the frames
-    are the same bytes under all three: `gpu` and `auto` send every baseline stream to the GPU, with restart intervals or without
-    (a scan without them is split among many lanes that synchronise themselves), `pil` none, or
+  * a directory of .png / .jpg frames, sorted by name: baseline JPEG files of one size go through the same GPU decoder, 8-bit grey,
+    grey + alpha, RGB and RGBA PNG files of one size through the GPU PNG decoder (articulation3d_amd/png.py: png_decode -- inflate,
+    Adler-32, unfiltering and the conversion in HIP), everything else (palette, 16-bit, interlaced, progressive or otherwise refused
+    files, frames a decoder flags) through PIL -- `--decoder auto|gpu|pil`, the frames are the same bytes under all three: `gpu`
+    sends every stream a decoder accepts to the GPU, `pil` none; `auto` sends every baseline JPEG stream, with restart intervals or
+    without (a scan without them is split among many lanes that synchronise themselves), and keeps PNG on PIL: one wave inflates one
+    frame, and at 8 - 90 frames per call that is slower than PIL on one host thread (MEASUREMENTS.md, "PNG decode"), or
   * `synthetic:N` / `synthetic:NxHxW` -- N seeded random frames (plumbing check), optionally at a source size H x W.
 The frames go to the GPU as they come from the reader (uint8 RGB, any size): the reference's `cv2.resize(im, (640, 480))` and
 BGR flip (:216-218) run on the device, fused with the normalisation in front of the stem (a3d_preprocess_resize_u8).
@@ -75,16 +78,53 @@ def gpu_decodes(info, decoder: str) -> bool:
     return decoder in ("gpu", "auto")
 
 
+PNG_AUTO_ON_GPU = False  # MEASUREMENTS.md, "PNG decode": the GPU path was not faster than PIL in every repetition of every class
+
+
+def gpu_decodes_png(info, decoder: str) -> bool:
+    """Whether a file that png_parse accepts goes to the GPU.  `pil`: never.  `gpu`: always.  `auto`: only where tools/png_decode_bench.py
+    found the GPU path faster than PIL in every repetition of every class of file (PNG_AUTO_ON_GPU; it did not: MEASUREMENTS.md, "PNG
+    decode"), and only on a machine with a GPU."""
+    if decoder == "gpu":
+        return True
+    return decoder == "auto" and PNG_AUTO_ON_GPU and torch.cuda.is_available()
+
+
+def _decode_pngs(blobs, frames, decoder: str) -> None:
+    """The PNG half of decode_images: the files png_parse accepts that share the first one's geometry, in one png_decode call."""
+    from articulation3d_amd.png import SIGNATURE, png_decode, png_parse
+
+    chosen, geometry = [], None
+    for k, blob in enumerate(blobs):
+        if blob[:8] != SIGNATURE:
+            continue
+        try:
+            info = png_parse(blob)
+        except ValueError:
+            continue
+        if gpu_decodes_png(info, decoder) and geometry in (None, info.geometry):
+            geometry = info.geometry
+            chosen.append(k)
+    if chosen:
+        out, status = png_decode([blobs[k] for k in chosen], strict=False)
+        out = out.cpu().numpy()
+        for i, k in enumerate(chosen):
+            if int(status[i]) == 0:
+                frames[k] = out[i]
+
+
 def decode_images(blobs, decoder: str = "auto") -> np.ndarray:
     """Encoded images (the bytes of .jpg / .png files or of an AVI's chunks) -> uint8 [n,H,W,3] RGB.  Baseline JPEG streams that share the
-    size and sampling of the first such stream are decoded on the GPU in one jpeg_decode call, the rest by PIL -- as is every frame the
-    GPU decoder flags (a damaged or out-of-domain stream), so the result is PIL's under every setting of `decoder`."""
+    size and sampling of the first such stream are decoded on the GPU in one jpeg_decode call, PNG files that share the first one's
+    geometry in one png_decode call (gpu_decodes / gpu_decodes_png say which), the rest by PIL -- as is every frame a GPU decoder
+    flags (a damaged or out-of-domain stream), so the result is PIL's under every setting of `decoder`."""
     import io
 
     from PIL import Image
 
     frames = [None] * len(blobs)
     if decoder != "pil":
+        _decode_pngs(blobs, frames, decoder)
         from articulation3d_amd.video import jpeg_decode, jpeg_parse
 
         chosen, geometry = [], None
@@ -293,8 +333,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fps", default=None,
                     help="--vis avi: frames per second, an integer or a ratio such as 30000/1001 (default: the rate of an .avi input, else 30)")
     ap.add_argument("--decoder", choices=("auto", "gpu", "pil"), default="auto",
-                    help="who decodes JPEG input (.avi chunks, .jpg files): gpu = every baseline stream on the GPU, pil = PIL on the host, auto = "
-                         "the GPU for the streams it was measured to decode faster (every baseline stream, with restart intervals or without); the frames are the same bytes")
+                    help="who decodes JPEG and PNG input (.avi chunks, .jpg and .png files): gpu = every baseline JPEG stream and every 8-bit "
+                         "non-interlaced grey / RGB (with or without alpha) PNG on the GPU, pil = PIL on the host, auto = the GPU for the streams it was "
+                         "measured to decode faster (every baseline JPEG stream; PNG stays on PIL: MEASUREMENTS.md, 'PNG decode'); the frames are the same bytes")
     ap.add_argument("--png-encoder", choices=("auto", "gpu", "pil"), default="auto",
                     help="who writes the --vis png files: gpu = filtering, LZ77 and Huffman coding on the GPU, only compressed bytes come to the "
                          "host; pil = the rows come to the host and PIL's zlib compresses them; auto = the GPU where it was measured faster "
